@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """bench.py — StoryGen denoising hot loop on MI355X: denoising steps/s at 512x512, 3 prior-frame context, bs=1.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps and times exactly K steps (`ms_per_step` = milliseconds per timed step), writes the
+outputs of the last timed step when --dump-outputs DIR is given, and prints the result line.  Everything else it can measure
+(the whole-image loop, the in-situ roofline, the fp8 deviation, the CPU baseline) runs only with --full.
+--dump-outputs DIR: the final latents of the timed window (what a caller of the sampler receives; all ranks, gathered) as
+DIR/latents.npy, float32.  Weights and inputs are seeded, so two builds given the same arguments can be compared output for output.
 
 One "step" = one iteration of /root/reference/model/pipeline.py:412-461 with classifier-free guidance: the reference
 passes over the R=3 prior frames + 1 main pass (batch 3, attn3 over 12 288 context tokens) + CFG + DDIM.  As written
@@ -16,7 +22,7 @@ Workload = BASELINE.json configs[1] ("inference.py: 50-step DDIM, 512x512, 3 pri
 (storygen_amd/synth.py) — there is no network for checkpoints.  N GPUs = N independent samples, one per GPU
 (weak scaling, no per-step communication; one RCCL all-gather of the final latents after the loop).
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  Extra objects (--full only):
   roofline     — the kernel family with the largest share of the step, timed in situ with HIP events on the launch
                  stream during one extra eager step after the timed region: achieved = algorithmic FLOPs of its
                  launches / their summed duration; peak = 2500 TFLOP/s dense fp16 MFMA
@@ -78,6 +84,7 @@ def cpu_baseline(arch, sd, inputs):
     sd = {k: v.float() for k, v in sd.items()}        # the cached state dict is stored as fp16 (exact); the oracle computes in fp32
     threads, nproc = _one_socket_cores()
     prev_threads = torch.get_num_threads()
+    threads = min(threads, prev_threads)               # an OMP_NUM_THREADS / CPU quota of the host caps it as well
     torch.set_num_threads(threads)
     sched = O.DDIM()
     t_main = sched.timesteps(T)[0]
@@ -112,6 +119,25 @@ def cpu_baseline(arch, sd, inputs):
             # workload when the full-depth golden was made in the build container (oracle/make_golden.py sd15_64_r3_full,
             # gpurun_out/golden_full.log: 2 693 s / 50 steps on 6 threads) — quoted, not re-timed here (it cannot travel)
             "reference_pipeline_seconds_per_step": 53.9, "reference_pipeline_threads": 6}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, arrays) -> None:
+    """--dump-outputs: every (name, tensor) as dirname/<name>.npy in float32 (float64 stays float64).  When the arrays together pass
+    DUMP_BUDGET_BYTES, each one larger than an even share of it is replaced by a fixed sample of its flattened elements: indices drawn
+    by a generator seeded with 0, so the same elements are written in every run."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, v in arrays.items():
+        if total > DUMP_BUDGET_BYTES and v.numel() * v.element_size() > share:
+            idx = torch.randint(v.numel(), (share // v.element_size(),), generator=torch.Generator().manual_seed(0))
+            v = v.flatten()[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), v.numpy())
 
 
 def measured_traffic(kernel: str):
@@ -261,31 +287,36 @@ def train_step_bench(args):
         loss, grads = step(batch)
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict({"loss": torch.as_tensor(loss, dtype=torch.float32).reshape(1)}, **grads))
     # forward FLOPs: 3 reference passes + main pass per sample; backward of the main pass counted as 2x its forward for the
     # dgrads + the attention recompute (SURVEY §8d config 4 estimate: ~23 TFLOP per step at bs=4)
     fwd = bs * (R * REF_GF + MAIN_GF) / 1000.0
-    # executed FLOPs of one step, counted: one extra EAGER step with every MFMA-class launch reporting its algorithmic FLOPs
-    # (GEMM / conv forward, dgrads and weight gradients, attention forward with 4 and backward with 6 + 8 N_q N_k D per head)
-    from storygen_amd import ops as _ops
-    sink = []
-    _ops.PROFILE_SINK = sink
-    try:
-        tr.train_step(batch)
-        torch.cuda.synchronize(dev)
-    finally:
-        _ops.PROFILE_SINK = None
-    fam = {}
-    for name, flops, a, b, _shape in sink:
-        f = fam.setdefault(name, {"launches": 0, "ms": 0.0, "gflop": 0.0})
-        f["launches"] += 1
-        f["ms"] += a.elapsed_time(b)
-        f["gflop"] += flops / 1e9
-    executed = sum(f["gflop"] for f in fam.values()) / 1e3
-    step_s = dt / args.steps
-    roof = {"bound": "mfma", "kernel": "whole training step (all MFMA-class launches)", "achieved": round(executed / step_s, 1),
-            "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s", "frac": round(executed / step_s / PEAK_FP16_TFLOPS, 4), "traffic": None,
-            "families": {k: {"launches": v["launches"], "ms": round(v["ms"], 3), "gflop": round(v["gflop"], 1),
-                             "tflops": round(v["gflop"] / v["ms"], 1) if v["ms"] > 0 else 0.0} for k, v in sorted(fam.items())}}
+    extra = {}
+    if args.full:
+        # executed FLOPs of one step, counted: one extra EAGER step with every MFMA-class launch reporting its algorithmic FLOPs
+        # (GEMM / conv forward, dgrads and weight gradients, attention forward with 4 and backward with 6 + 8 N_q N_k D per head)
+        from storygen_amd import ops as _ops
+        sink = []
+        _ops.PROFILE_SINK = sink
+        try:
+            tr.train_step(batch)
+            torch.cuda.synchronize(dev)
+        finally:
+            _ops.PROFILE_SINK = None
+        fam = {}
+        for name, flops, a, b, _shape in sink:
+            f = fam.setdefault(name, {"launches": 0, "ms": 0.0, "gflop": 0.0})
+            f["launches"] += 1
+            f["ms"] += a.elapsed_time(b)
+            f["gflop"] += flops / 1e9
+        executed = sum(f["gflop"] for f in fam.values()) / 1e3
+        step_s = dt / args.steps
+        roof = {"bound": "mfma", "kernel": "whole training step (all MFMA-class launches)", "achieved": round(executed / step_s, 1),
+                "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s", "frac": round(executed / step_s / PEAK_FP16_TFLOPS, 4), "traffic": None,
+                "families": {k: {"launches": v["launches"], "ms": round(v["ms"], 3), "gflop": round(v["gflop"], 1),
+                                 "tflops": round(v["gflop"] / v["ms"], 1) if v["ms"] > 0 else 0.0} for k, v in sorted(fam.items())}}
+        extra = {"tflop_per_step_executed": round(executed, 3), "roofline": roof}
     print(json.dumps({"metric": "stage-2 training steps/sec @512x512, bs=4, 3 reference frames (non-contract)",
                       "value": round(args.steps / dt, 4), "unit": "it/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                       "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -295,7 +326,7 @@ def train_step_bench(args):
                                              + ("eager launches" if args.no_graph else "whole step = one hipGraph replay, loss-scaled fp16 gradient operands"),
                                  "hipgraph": not args.no_graph, "grad_scale": tr.last_grad_scale, "gradients": len(grads), "loss": float(loss),
                                  "optimizer": args.optimizer + ("" if args.optimizer == "none" else " + clip_grad_norm_(1.0), in the timed step")},
-                      "tflop_forward_per_step": round(fwd, 3), "tflop_per_step_executed": round(executed, 3), "roofline": roof}), flush=True)
+                      "tflop_forward_per_step": round(fwd, 3), **extra}), flush=True)
 
 
 def default_ref_ahead(args) -> int:
@@ -308,8 +339,8 @@ def default_ref_ahead(args) -> int:
 
 
 def cached_state_dict(arch, seed: int, rank: int, use_dist: bool):
-    """synth.synthetic_state_dict(arch, seed), synthesised ONCE per node: the first local rank draws the 909 M parameters (a minute of
-    host time) and stores them as fp16 — lossless, the values are fp16-exact — under the temp directory; every other rank (and every
+    """synth.synthetic_state_dict(arch, seed), synthesised ONCE per node: the first local rank draws the 909 M parameters (seconds:
+    one tensor per host thread) and stores them as fp16 — lossless, the values are fp16-exact — under the temp directory; every other rank (and every
     later bench.py run on the box) memory-maps the file.  Before round 6 each of N ranks synthesised all of it, sharing the host's
     cores.  The file name carries a hash of the architecture, the seed and synth.py itself."""
     import hashlib
@@ -322,7 +353,7 @@ def cached_state_dict(arch, seed: int, rank: int, use_dist: bool):
     first = int(os.environ.get("LOCAL_RANK", rank)) == 0
     sd = None
     if first and not os.path.exists(path):
-        sd = synth.synthetic_state_dict(arch, seed)
+        sd = synth.synthetic_state_dict(arch, seed, workers=torch.get_num_threads())     # one tensor per host thread: seconds, not a minute
         try:
             tmp = f"{path}.{os.getpid()}.tmp"
             torch.save({k: v.to(torch.float16) for k, v in sd.items()}, tmp)
@@ -336,7 +367,7 @@ def cached_state_dict(arch, seed: int, rank: int, use_dist: bool):
         try:
             sd = torch.load(path, mmap=True, weights_only=True)
         except Exception:
-            sd = synth.synthetic_state_dict(arch, seed)
+            sd = synth.synthetic_state_dict(arch, seed, workers=torch.get_num_threads())
     return sd
 
 
@@ -469,14 +500,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the whole-image loop, the in-situ roofline (--train-step: the counted executed FLOPs), "
+                         "the fp8 deviation and the CPU baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the final latents; with "
+                         "--train-step the loss and the gradients (a fixed, seeded sample of them past 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--dry-run", action="store_true",
                     help="TEST ONLY, measures nothing: the launcher path (torch.distributed.run ranks, barrier, max-over-ranks timing, the "
                          "final all-gather, the per-rank-distinct check, the JSON line) on the CPU with the gloo backend and a stand-in "
                          "engine (tests/stub_engine.py) on a tiny UNet description; the JSON says dry_run and carries value null")
     ap.add_argument("--dump-algorithmic", default=None, metavar="PATH",
-                    help="write the algorithmic bytes per profiler class (kernel instantiation | grid) of the instrumented step to PATH "
-                         "(tools/traffic_from_pmc.py merges it into profiles/traffic.json)")
+                    help="with --full: write the algorithmic bytes per profiler class (kernel instantiation | grid) of the instrumented step "
+                         "to PATH (tools/traffic_from_pmc.py merges it into profiles/traffic.json)")
     ap.add_argument("--stage", choices=("multi-image-condition", "auto-regressive"), default="multi-image-condition",
                     help="multi-image-condition = the contract line (SURVEY 8d); auto-regressive = the mode /root/reference/inference.py:133 "
                          "defaults to (every prior frame at its own noise level: 2R distinct reference samples per step instead of R + 1) — "
@@ -511,7 +548,8 @@ def main():
                     help="A/B (changes results, never the contract line): fp16 residual stream inside the transformer blocks")
     ap.add_argument("--no-gemm-pairs", action="store_true", help="A/B: q|k + V^T, q2 + q3, k3 + v3^T as separate launches")
     ap.add_argument("--attn-pair", action="store_true", help="A/B: text and image cross-attention of a block in one launch")
-    ap.add_argument("--no-loop", action="store_true", help="skip the whole-image line (loop_50_steps_ms: prepare() + all 50 steps, two repeats)")
+    ap.add_argument("--no-loop", action="store_true",
+                    help="with --full: skip the whole-image line (loop_50_steps_ms: prepare() + all 50 steps, two repeats)")
     ap.add_argument("--no-time-tables", action="store_true",
                     help="A/B switch: every UNet call recomputes the time-embedding chain (as written) instead of reading the rows tabulated at prepare()")
     ap.add_argument("--no-short-rows", action="store_true",
@@ -538,6 +576,8 @@ def main():
                     help="NOT the contract workload: BASELINE configs[3] — stage-2 training step, bs=4, 512x512, 3 reference frames "
                          "(forward of 3 reference passes + main pass, backward of the main pass, 80 attn3 gradients); reports it/s")
     args = ap.parse_args()
+    if args.dump_algorithmic and not args.full:
+        ap.error("--dump-algorithmic needs --full (it comes from the instrumented step of the roofline)")
     if args.train_step:
         return train_step_bench(args)
 
@@ -633,10 +673,12 @@ def main():
     final, gather_ms, finite = gather_and_check(sampler, world, dev)
     distinct = True                                             # asserted by gather_and_check
     sampler.check_guards()                                      # the LayerNorm fold stayed inside its range (raises otherwise)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latents": final})     # before --full's loop: `final` is the sampler's own buffer on one rank
     # one whole image, prepare() to last step (not the contract's `value`: the steady-state window above is)
     loop_ms = loop_prep = None
     n_loop = -(-T // G) * G
-    if not args.no_loop and not args.no_graph:
+    if args.full and not args.no_loop and not args.no_graph:
         loop_ms, loop_prep = timed_loop(sampler, inputs, n_loop, args.stage, use_dist, dev)
         sampler.check_guards()
 
@@ -675,14 +717,15 @@ def main():
                            "includes": "prepare() (text K/V, time tables, un-overlapped primer reference pass) + run(); last group without look-ahead pass",
                            "ms_per_step_over_the_loop": round(best / n_loop, 3),
                            "overhead_ms_per_step_vs_steady_state": round(best / n_loop - 1e3 * dt / args.steps, 3)}
-        out["roofline"], executed = in_situ_roofline(sampler, args.dump_algorithmic)
-        if args.config5_shape:
-            out["roofline"]["traffic"] = None          # profiles/traffic.json was measured on the contract workload
-        out["tflop_per_step_executed"] = round(executed, 3)
-        out["mfma_frac_whole_step"] = round(value * executed / (world * PEAK_FP16_TFLOPS), 4)
         out["sample_forwards_per_step"] = {"reference": sampler.executed_sample_forwards()[0],
                                            "main": sampler.executed_sample_forwards()[1], "as_written": 3 * n_ref + 3}
-        if args.fp8_attention:
+        if args.full:
+            out["roofline"], executed = in_situ_roofline(sampler, args.dump_algorithmic)
+            if args.config5_shape:
+                out["roofline"]["traffic"] = None          # profiles/traffic.json was measured on the contract workload
+            out["tflop_per_step_executed"] = round(executed, 3)
+            out["mfma_frac_whole_step"] = round(value * executed / (world * PEAK_FP16_TFLOPS), 4)
+        if args.full and args.fp8_attention:
             # the e4m3 path is the throughput OPTION BASELINE configs[4] names, not a parity path: state what it costs in accuracy next to
             # what it buys (since round 5: nothing — the fp16 D = 40 kernel got the softmax-in-MFMA work, the e4m3 kernel did not)
             n_cmp = 2 * G if G > 1 else 10
@@ -698,7 +741,7 @@ def main():
                                               "--config5-shape line) and outside the 1e-3 parity bar (3.9e-3 .. 7.6e-3 vs the oracle golden, "
                                               "tests/test_unet_gpu.py); kept as an opt-in, the product default for config 5 is fp16"}
             del ref16
-        if world == 1 and not args.no_cpu_baseline and not args.config5_shape:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.config5_shape:
             out["cpu_baseline"] = cpu_baseline(arch, sd, inputs)
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -46,33 +46,42 @@ def synthetic_tensor(name: str, shape, seed: int = 0, std: float = 1.0) -> torch
     return fp16_exact(torch.randn(tuple(shape), generator=_gen(name, seed), dtype=torch.float32) * std)
 
 
-def synthetic_state_dict(arch: UNetArch, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
-    """fp32 CPU state dict with the reference's keys and shapes."""
-    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
-    for name, shape in param_shapes(arch).items():
-        g = _gen(name, seed)
-        is_norm = (".norm" in name or name.startswith("conv_norm_out")) and len(shape) == 1
-        if is_norm:
-            if name.endswith("weight"):
-                t = 1.0 + 0.1 * torch.randn(shape, generator=g)
-            else:
-                t = 0.1 * torch.randn(shape, generator=g)
+def _synthetic_param(arch: UNetArch, name: str, shape, seed: int) -> torch.Tensor:
+    g = _gen(name, seed)
+    is_norm = (".norm" in name or name.startswith("conv_norm_out")) and len(shape) == 1
+    if is_norm:
+        if name.endswith("weight"):
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g)
         else:
-            if name.endswith("weight"):
-                fan_in = 1
-                for d in shape[1:]:
-                    fan_in *= d
-            else:  # bias: fan_in of the matching weight
-                wshape = param_shapes_cache(arch)[name[:-4] + "weight"]
-                fan_in = 1
-                for d in wshape[1:]:
-                    fan_in *= d
-            bound = 1.0 / math.sqrt(fan_in)
-            t = (torch.rand(shape, generator=g) * 2.0 - 1.0) * bound
-            if name.endswith("to_q.weight") or name.endswith("to_k.weight"):
-                t = t * QK_GAIN
-        sd[name] = fp16_exact(t)
-    return sd
+            t = 0.1 * torch.randn(shape, generator=g)
+    else:
+        if name.endswith("weight"):
+            fan_in = 1
+            for d in shape[1:]:
+                fan_in *= d
+        else:  # bias: fan_in of the matching weight
+            wshape = param_shapes_cache(arch)[name[:-4] + "weight"]
+            fan_in = 1
+            for d in wshape[1:]:
+                fan_in *= d
+        bound = 1.0 / math.sqrt(fan_in)
+        t = (torch.rand(shape, generator=g) * 2.0 - 1.0) * bound
+        if name.endswith("to_q.weight") or name.endswith("to_k.weight"):
+            t = t * QK_GAIN
+    return fp16_exact(t)
+
+
+def synthetic_state_dict(arch: UNetArch, seed: int = 0, workers: int = 1) -> "OrderedDict[str, torch.Tensor]":
+    """fp32 CPU state dict with the reference's keys and shapes.  workers > 1 draws the tensors on that many host
+    threads: every tensor has its own generator, so the values are the same as with one."""
+    shapes = param_shapes(arch)
+    param_shapes_cache(arch)
+    if workers <= 1:
+        return OrderedDict((name, _synthetic_param(arch, name, shape, seed)) for name, shape in shapes.items())
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(workers) as ex:
+        tensors = list(ex.map(lambda item: _synthetic_param(arch, item[0], item[1], seed), shapes.items()))
+    return OrderedDict(zip(shapes, tensors))
 
 
 _shape_cache: Dict[int, "OrderedDict[str, tuple]"] = {}

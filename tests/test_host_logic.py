@@ -630,6 +630,40 @@ def test_bench_argument_parser_builds():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-500:]
     assert "--gpus" in r.stdout and "--steps" in r.stdout and "--warmup" in r.stdout
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_bench_dump_outputs_format_and_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy files (float64 kept), exact below the budget; above it, the arrays past their share are
+    replaced by a sample of their elements that is the same in every run."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    g = torch.Generator().manual_seed(5)
+    small = torch.randn(1, 4, 8, 8, generator=g, dtype=torch.float16)
+    dbl = torch.randn(3, generator=g, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"latents": small, "d": dbl})
+    a = np.load(tmp_path / "a" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 4, 8, 8) and np.array_equal(a, small.float().numpy())
+    assert np.load(tmp_path / "a" / "d.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+    big = torch.randn(10_000, generator=g)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert b.dtype == np.float32 and b.nbytes <= 2048 and np.array_equal(b, c) and np.isin(b, big.numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "b" / "small.npy"), small.float().numpy())
+
+
+def test_synthetic_state_dict_is_the_same_on_many_threads():
+    """bench.py synthesises the weights on all host threads (synth.synthetic_state_dict(workers=N)): the same tensors as one thread."""
+    from storygen_amd.arch import build_arch
+    from storygen_amd.synth import synthetic_state_dict
+    arch = build_arch(dict(block_out_channels=(32, 64), down_block_types=("CrossAttnDownBlock2D", "DownBlock2D"),
+                           up_block_types=("UpBlock2D", "CrossAttnUpBlock2D"), cross_attention_dim=48))
+    a, b = synthetic_state_dict(arch, 3), synthetic_state_dict(arch, 3, workers=4)
+    assert list(a) == list(b) and all(torch.equal(a[k], b[k]) for k in a)
 
 
 def _all_tensors(obj, prefix=""):

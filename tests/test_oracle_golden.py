@@ -229,10 +229,9 @@ def test_vae_oracle_structure():
     from oracle import encoders_oracle as eo
     sd = eo.vae_random_state()
     assert sum(v.numel() for v in sd.values()) == 83_653_863
-    cfg_path = "/root/reference/ckpt/stable-diffusion-v1-5/vae/config.json"
-    if os.path.exists(cfg_path):
-        cfg = json.load(open(cfg_path))
-        assert tuple(cfg["block_out_channels"]) == (128, 256, 512, 512) and cfg["layers_per_block"] == 2 and cfg["latent_channels"] == 4
+    with open(os.path.join(GOLDEN, "sd15_vae_config.json")) as f:     # the reference checkpoint's vae/config.json
+        cfg = json.load(f)
+    assert tuple(cfg["block_out_channels"]) == (128, 256, 512, 512) and cfg["layers_per_block"] == 2 and cfg["latent_channels"] == 4
     small = eo.vae_random_state(block_out=(32, 64), layers_per_block=1, seed=1)
     x = torch.rand(2, 3, 16, 24)
     m = eo.vae_encode_moments(small, x)

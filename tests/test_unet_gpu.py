@@ -6,6 +6,7 @@ north-star bar is 1e-3 relative on the latents; per-tensor bars for intermediate
 single fp16 rounding of an activation is already 2^-11 = 4.9e-4 relative."""
 import os
 
+import numpy as np
 import pytest
 import torch
 
@@ -730,19 +731,24 @@ def test_config5_fp8_attention_vs_oracle_golden_96x96_r5(gpu, sd15, G):
     assert max(errs) <= 1.5e-2, errs
 
 
-def test_bench_multi_gpu_path_over_rccl_with_one_rank(gpu):
+def test_bench_multi_gpu_path_over_rccl_with_one_rank(gpu, tmp_path):
     """The N > 1 code path of bench.py (torch.distributed.run launch, RCCL init, barrier, max-over-ranks, the single all-gather
-    of the final latents) exercised with the one GPU this box has: world_size 1 through the same launcher the driver uses."""
+    of the final latents) exercised with the one GPU this box has: world_size 1 through the same launcher the driver uses.
+    --dump-outputs writes the gathered final latents (float32)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+           "--dump-outputs", str(tmp_path)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
     res = json.loads(line)
     assert res["n_gpus"] == 1 and res["latents_gathered"] == 1 and res["latents_finite"] and res["latents_distinct_per_rank"]
     assert res["config"]["parallelism"].startswith("dp1") and res["value"] > 0
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    lat = np.load(tmp_path / "latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (1, 4, 64, 64) and np.isfinite(lat).all()

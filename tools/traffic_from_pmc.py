@@ -1,11 +1,11 @@
 #!/usr/bin/env python
 """profiles/traffic.json from two rocprofv3 PMC passes over `python bench.py ...` (FETCH_SIZE pass, WRITE_SIZE pass).
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out/f -o p -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d out/w -o p -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out/f -o p -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d out/w -o p -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
     python tools/traffic_from_pmc.py out/f/p_counter_collection.csv out/w/p_counter_collection.csv "<provenance note>" [algorithmic.json]
 
-algorithmic.json = `python bench.py --dump-algorithmic algorithmic.json` of the same build: the ALGORITHMIC bytes per launch of every
+algorithmic.json = `python bench.py --full --dump-algorithmic algorithmic.json` of the same build: the ALGORITHMIC bytes per launch of every
 GEMM / convolution class (kernel instantiation | grid), which the PMC classes are then set beside (`algorithmic_mbytes_per_launch`,
 `hbm_over_algorithmic`; a split-K class's second pass is its own kernel and is not in the algorithmic figure).
 
