@@ -405,6 +405,15 @@ int sg_cfg_ddim_step_f32(const float* eps3, float* latents, float* latents3, con
  *     latents; if keep: kept <- latents; latents <- A x_src - Bc e' (and the three-fold `latents3`, if non-NULL). */
 int sg_cfg_plms_step_f32(const float* eps3, float* latents, float* latents3, float* history, float* kept,
                          const float* coef, int32_t N, int64_t n, sg_stream_t stream);
+/* sg_cfg_dpm_step_f32: the same guidance combine followed by one multistep DPM-Solver / DPM-Solver++ update of diffusers'
+ *     DPMSolverMultistepScheduler (model/pipeline.py:7-16 accepts it; call site :461) — convert_model_output plus
+ *     dpm_solver_first_order_update / multistep_dpm_solver_second_order_update / multistep_dpm_solver_third_order_update, every
+ *     order and variant reduced to one linear form: coef = {s_img, s_txt, cx, ce, A, w0, w1, w2, slot_cur, slot1, slot2, push}
+ *     (12 floats, integers stored as floats).  m = cx latents + ce eps (the converted model output);
+ *     latents <- A latents + w0 m + w1 history[slot1] + w2 history[slot2] (a slot whose weight is 0 is not read); if push:
+ *     history[slot_cur] <- m (history = 3 x [N*n] fp32 ring); the three-fold `latents3` too, if non-NULL. */
+int sg_cfg_dpm_step_f32(const float* eps3, float* latents, float* latents3, float* history, const float* coef, int32_t N,
+                        int64_t n, sg_stream_t stream);
 
 /* Strided, batched 2-D copy of rows: dst[b][r][0:cols] = src[b][r][0:cols] (cols % 8 == 0; strides in elements).
  * mode 0: fp16 -> fp16, 1: fp32 -> fp32, 2: fp32 -> fp16 (cast).

@@ -259,6 +259,33 @@ __global__ void cfg_plms_kernel(const float* eps3, float* lat, float* lat3, floa
     }
 }
 
+// DPM-Solver multistep update (diffusers DPMSolverMultistepScheduler.convert_model_output + dpm_solver_first_order_update /
+// multistep_dpm_solver_{second,third}_order_update, epsilon prediction): coef = [s_img, s_txt, cx, ce, A, w0, w1, w2, slot_cur,
+// slot1, slot2, push] (storygen_amd/scheduler.py::DPMSolverMultistepSchedule.step_row).  hist = 3-slot ring of converted model
+// outputs (x0 for dpmsolver++, epsilon for dpmsolver), fp32: x0 near t = 999 is (x - sigma e) / alpha with alpha ~ 0.07.
+__global__ void cfg_dpm_kernel(const float* eps3, float* lat, float* lat3, float* hist, const float* coef, int N, long n) {
+    const long total = (long)N * n;
+    const float s_img = coef[0], s_txt = coef[1], cx = coef[2], ce = coef[3], A = coef[4];
+    const float w0 = coef[5], w1 = coef[6], w2 = coef[7];
+    // slot indices are clamped to the ring: a malformed table row can never address memory outside `hist`
+    const int cur = min(max((int)coef[8], 0), 2), s1 = min(max((int)coef[9], 0), 2), s2 = min(max((int)coef[10], 0), 2);
+    const bool push = coef[11] != 0.f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const float eu = eps3[i], ei = eps3[total + i], ea = eps3[2 * total + i];
+        const float e = eu + s_img * (ei - eu) + s_txt * (ea - ei);
+        const float x = lat[i];
+        const float m = cx * x + ce * e;
+        // history terms are read before the store (slot_cur never aliases slot1 / slot2) and only when their weight is non-zero:
+        // a ring slot left over from an earlier loop (or never written) must not reach the first calls as 0 * NaN
+        float xp = A * x + w0 * m;
+        if (w1 != 0.f) xp += w1 * hist[s1 * total + i];
+        if (w2 != 0.f) xp += w2 * hist[s2 * total + i];
+        if (push) hist[cur * total + i] = m;
+        lat[i] = xp;
+        if (lat3) { lat3[i] = xp; lat3[total + i] = xp; lat3[2 * total + i] = xp; }
+    }
+}
+
 // mode 0: fp16 -> fp16, 1: fp32 -> fp32, 2: fp32 -> fp16 (cast); 8 elements per thread per iteration
 __global__ __launch_bounds__(256) void copy_rows_kernel(void* dst, long ldd, long bsd, const void* src, long lds, long bss,
                                                         int batches, int rows, int cols, int mode) {
@@ -396,6 +423,16 @@ extern "C" int sg_cfg_plms_step_f32(const float* eps3, float* latents, float* la
     hipLaunchKernelGGL(cfg_plms_kernel, dim3((int)min((long)1024, (total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, eps3,
                        latents, latents3, history, kept, coef, N, (long)n);
     SG_CHECK_LAUNCH("sg_cfg_plms_step_f32");
+    return SG_OK;
+}
+
+extern "C" int sg_cfg_dpm_step_f32(const float* eps3, float* latents, float* latents3, float* history, const float* coef, int32_t N,
+                                   int64_t n, sg_stream_t stream) {
+    SG_REQUIRE(eps3 && latents && history && coef && N > 0 && n > 0, "sg_cfg_dpm_step: bad arguments");
+    const long total = (long)N * n;
+    hipLaunchKernelGGL(cfg_dpm_kernel, dim3((int)min((long)1024, (total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, eps3,
+                       latents, latents3, history, coef, N, (long)n);
+    SG_CHECK_LAUNCH("sg_cfg_dpm_step_f32");
     return SG_OK;
 }
 

@@ -11,11 +11,12 @@ Deliberate differences from the reference, none of which changes latents:
     inner loop variable shadows `i`, pipeline.py:412,418 — SURVEY F6f);
   * `guidance_scale <= 1` raises (the reference's non-CFG branch passes a list where a tensor is required and cannot
     run, :430 — SURVEY F6g);
-  * schedulers: DDIM (what the reference ships and uses, inference.py:48) and PNDM with `skip_prk_steps=true` (the class
-    named by ckpt/stable-diffusion-v1-5/scheduler/scheduler_config.json); `scheduler` may be a
-    storygen_amd.scheduler.DDIMSchedule / PNDMSchedule or any object whose `.config` carries the diffusers keys
-    (`_class_name` or the object's class name selects the rule).  Anything else (Euler, LMS, DPM-solver, v-prediction,
-    clip_sample) raises instead of silently running DDIM.
+  * schedulers: DDIM (what the reference ships and uses, inference.py:48), PNDM with `skip_prk_steps=true` (the class
+    named by ckpt/stable-diffusion-v1-5/scheduler/scheduler_config.json) and DPMSolverMultistepScheduler (DPM-Solver++(2M) by
+    default, :7-16 accepts it); `scheduler` may be a storygen_amd.scheduler.DDIMSchedule / PNDMSchedule /
+    DPMSolverMultistepSchedule or any object whose `.config` carries the diffusers keys (`_class_name` or the object's class name
+    selects the rule).  Anything else (Euler, EulerAncestral, LMS — their add_noise cannot take the reference pass's t / 10 —,
+    v-prediction, clip_sample, thresholding) raises instead of silently running DDIM.
 """
 from __future__ import annotations
 
@@ -36,7 +37,8 @@ def _as_schedule(scheduler) -> DDIMSchedule:
         return scheduler
     cfg = getattr(scheduler, "config", None)
     if cfg is None:
-        raise TypeError("scheduler must be a DDIMSchedule / PNDMSchedule or expose a diffusers-style .config")
+        raise TypeError("scheduler must be a DDIMSchedule / PNDMSchedule / DPMSolverMultistepSchedule or expose a diffusers-style "
+                        ".config")
     return schedule_from_config(cfg, type(scheduler).__name__)
 
 
@@ -241,7 +243,7 @@ class StableDiffusionPipeline:
         schedule = _as_schedule(self.scheduler)
         # group schedule (sampler ref_ahead): the reference passes of 5 consecutive steps as one batched UNet call inside one hipGraph per
         # group — when nobody watches the intermediate latents (a callback sees every step: step-by-step graphs then) and the number of
-        # UNet evaluations is a multiple of 5 (DDIM: 50 steps -> 50; PNDM: n + 1)
+        # UNet evaluations is a multiple of 5 (DDIM, DPM-Solver: n steps -> n; PNDM: n + 1)
         evals = len(schedule.timesteps(num_inference_steps))
         G = 5 if (callback is None and stage in STAGES[:2] and evals % 5 == 0) else 1
         key = (n, h, w, R, text.shape[1], id(wts), schedule.key(), G)

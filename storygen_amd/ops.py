@@ -816,6 +816,22 @@ def cfg_plms_step(eps3: torch.Tensor, latents: torch.Tensor, latents3: Optional[
     return latents
 
 
+def cfg_dpm_step(eps3: torch.Tensor, latents: torch.Tensor, latents3: Optional[torch.Tensor], history: torch.Tensor,
+                 coef: torch.Tensor) -> torch.Tensor:
+    """Guidance combine + DPM-Solver multistep update (sg_cfg_dpm_step_f32); history fp32 [3, *latents.shape] (converted model
+    outputs), coef = the 2 guidance scales + DPMSolverMultistepSchedule.step_row (12 floats)."""
+    for n, t in (("eps3", eps3), ("latents", latents), ("history", history), ("coef", coef)):
+        _f32(t, n)
+    if history.numel() != 3 * latents.numel() or coef.numel() != 12 or eps3.numel() != 3 * latents.numel():
+        raise ValueError("cfg_dpm_step: eps3 and history must hold 3 latents each, coef 12 floats")
+    if latents3 is not None and (latents3.dtype != torch.float32 or latents3.numel() != 3 * latents.numel()):
+        raise ValueError("cfg_dpm_step: latents3 must be fp32 and hold 3 latents")
+    N = latents.shape[0]
+    check(lib.sg_cfg_dpm_step_f32(eps3.data_ptr(), latents.data_ptr(), _p(latents3), history.data_ptr(), coef.data_ptr(), N,
+                                  latents[0].numel(), _stream()), "sg_cfg_dpm_step_f32")
+    return latents
+
+
 def copy_rows(dst: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
     """dst[b, r, :cols] = src[b, r, :cols] for 3-D views with unit channel stride; fp16->fp16, fp32->fp32 or
     fp32->fp16 (cast)."""

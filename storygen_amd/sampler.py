@@ -3,7 +3,8 @@
 One `step()` is one iteration of /root/reference/model/pipeline.py:412-461 with classifier-free guidance: the
 reference passes that harvest the 16 diffusion features of every prior frame (:418-438), one main pass (batch 3N:
 latents x3 with [uncond, uncond, text]) whose attn3 cross-attends to them (:440-453), the 3-way guidance combine
-(:457-458) and the DDIM update (:461).
+(:457-458) and the scheduler's update (:461): DDIM, PNDM/PLMS or multistep DPM-Solver, each one elementwise kernel driven by a
+row of host-computed scalars per step (storygen_amd/scheduler.py), so the step graph is the same for all three.
 
 MI355X-first structure
   * The R reference passes are ONE batched UNet call.  As written, pass i runs the batch [zero_i, img_i, img_i] with
@@ -17,7 +18,7 @@ MI355X-first structure
   * A reference pass ends at its last harvest point (the epsilon it would go on to produce is discarded by the loop,
     :433-435), and the text K/V projections, which do not depend on the timestep, are computed once per prompt.
   * The whole step is ONE hipGraph replayed per step; everything that changes between steps — timesteps, add_noise
-    and DDIM coefficients — lives in a small device buffer refreshed by one async H2D copy from a pinned table.
+    and update-rule coefficients — lives in a small device buffer refreshed by one async H2D copy from a pinned table.
     Latents stay fp32 across steps.
   * The reference pass does not depend on the latents (its inputs are the prior frames noised to ref_t,
     pipeline.py:414-427), only the main pass does.  With `overlap` (default, graph mode) the captured graph of step k
@@ -144,6 +145,8 @@ class StoryGenSampler:
         if self.schedule.kind == "plms":          # PNDM: ring of the last 4 guided epsilons + the sample kept by the first call
             self.eps_history = torch.zeros((4,) + lat_shape, **f32)
             self.kept_sample = torch.zeros(lat_shape, **f32)
+        elif self.schedule.kind == "dpm":         # DPM-Solver: ring of the last 3 converted model outputs (fp32: x0 = (x - sigma e) / alpha)
+            self.model_outputs = torch.zeros((3,) + lat_shape, **f32)
         self.table: Optional[torch.Tensor] = None
         self.num_steps = 0
         self.k = 0
@@ -417,6 +420,8 @@ class StoryGenSampler:
         eps3 = main.forward(consume=not self.no_ctx, text_cache=True, side=self.side_main)
         if self.schedule.kind == "plms":                                                  # :457-461
             ops.cfg_plms_step(eps3, self.latents, self.latents3, self.eps_history, self.kept_sample, cd)
+        elif self.schedule.kind == "dpm":
+            ops.cfg_dpm_step(eps3, self.latents, self.latents3, self.model_outputs, cd)
         else:
             ops.cfg_ddim_step(eps3, self.latents, self.latents3, cd)
 
@@ -665,7 +670,7 @@ def step_table(schedule: DDIMSchedule, ts, num_inference_steps: int, units0, R: 
     """The scalars every denoising step needs, as rows of the pinned table the sampler uploads from (pure host logic).
 
     Row k = [U reference timesteps | B main timesteps | U x 2 add_noise coefficients | 2 guidance scales + the update
-    rule's scalars (schedule.step_row: 4 for DDIM, 13 for PNDM/PLMS)], U = G * len(units0).  units0 = the (kind, frame, sample) reference samples of ONE step.
+    rule's scalars (schedule.step_row: 4 for DDIM, 13 for PNDM/PLMS, 10 for DPM-Solver)], U = G * len(units0).  units0 = the (kind, frame, sample) reference samples of ONE step.
     Which reference scalars row k carries depends on the schedule of the passes:
       no overlap          : those of step k itself (reference pass, then main pass);
       overlap, G = 1      : those of step k+1 (graph k runs main pass k beside reference pass k+1);

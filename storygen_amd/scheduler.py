@@ -5,11 +5,14 @@ DDIMSchedule: computed exactly as diffusers' DDIMScheduler does for the schedule
 clip_sample=False, eta=0).  PNDMSchedule: the class the shipped ckpt/stable-diffusion-v1-5/scheduler/scheduler_config.json
 names (`_class_name: PNDMScheduler`, skip_prk_steps=true) — the PLMS linear-multistep rule of diffusers 0.13.1
 (`PNDMScheduler.step_plms` / `_get_prev_sample`), restated from the published algorithm (diffusers is not installed here).
+DPMSolverMultistepSchedule: DPM-Solver / DPM-Solver++ multistep (diffusers 0.13.1 `DPMSolverMultistepScheduler`, which
+model/pipeline.py:7-16 also accepts), restated from the published formulas (Lu et al. 2022, "DPM-Solver" and "DPM-Solver++").
 Reference call sites: model/pipeline.py:7-16,47-75 (accepted scheduler classes), :366-367 (set_timesteps), :420-424
 (add_noise), :461 (step)."""
 from __future__ import annotations
 
 import json
+import math
 import os
 from typing import List, Optional
 
@@ -22,7 +25,8 @@ _IGNORED_KEYS = ("_class_name", "_diffusers_version", "_name_or_path", "_use_def
 
 
 class DDIMSchedule:
-    kind = "ddim"          # which update kernel the sampler launches (ddim: sg_cfg_ddim_step_f32, plms: sg_cfg_plms_step_f32)
+    kind = "ddim"          # which update kernel the sampler launches (ddim: sg_cfg_ddim_step_f32, plms: sg_cfg_plms_step_f32,
+    #                        dpm: sg_cfg_dpm_step_f32)
     row_len = 4            # floats step_row() contributes to a row of the sampler's per-step table
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
@@ -179,9 +183,135 @@ class PNDMSchedule(DDIMSchedule):
         return [A, Bc, *w, float(cur), *map(float, sl), float(push), float(k == 1), float(k == 0)]
 
 
+# keys of a DDIM / PNDM config that do not apply to DPM-Solver: diffusers ignores them the same way in
+# `DPMSolverMultistepScheduler.from_config(ddim.config)`, the usual way of switching schedulers
+_DPM_IGNORED_KEYS = _IGNORED_KEYS + ("steps_offset", "set_alpha_to_one", "clip_sample")
+
+
+class DPMSolverMultistepSchedule(DDIMSchedule):
+    """diffusers 0.13.1 DPMSolverMultistepScheduler (epsilon prediction, no thresholding), the multistep DPM-Solver of
+    Lu et al. 2022: "DPM-Solver++(2M)" with the defaults solver_order=2, algorithm_type="dpmsolver++".
+
+    Timesteps: linspace(0, T - 1, n + 1).round()[::-1][:-1] (n UNet evaluations, 999, 949, .. for n = 20, T = 1000); the step
+    after the last one goes to timestep 0 (alphas_cumprod[0]).  With alpha = sqrt(abar), sigma = sqrt(1 - abar),
+    lambda = log alpha - log sigma, h = lambda_t - lambda_s0 (s0 = this call's timestep, t = the next one), and m_j the
+    converted model output of the call j steps back (`convert_model_output`: x0 = (x - sigma_s e) / alpha_s for dpmsolver++,
+    e itself for dpmsolver), one call of `step` is
+        first order  (`dpm_solver_first_order_update`):   x' = A x + c D0
+        second order (`multistep_dpm_solver_second_order_update`, r0 = h_0 / h):
+                     D1 = (m0 - m1) / r0,  x' = A x + c D0 + b D1          (midpoint: b = c / 2)
+        third order  (`multistep_dpm_solver_third_order_update`, r1 = h_1 / h):
+                     D1_0 = (m0 - m1) / r0,  D1_1 = (m1 - m2) / r1,  D1 = D1_0 + r0 / (r0 + r1) (D1_0 - D1_1),
+                     D2 = (D1_0 - D1_1) / (r0 + r1),  x' = A x + c D0 + b D1 + d D2
+    with, for dpmsolver++: A = sigma_t / sigma_s0, c = -alpha_t (e^-h - 1), b (heun, 3rd order) = alpha_t ((e^-h - 1) / h + 1),
+    d = -alpha_t ((e^-h - 1 + h) / h^2 - 0.5); for dpmsolver: A = alpha_t / alpha_s0, c = -sigma_t (e^h - 1),
+    b (heun, 3rd order) = -sigma_t ((e^h - 1) / h - 1), d = -sigma_t ((e^h - 1 - h) / h^2 - 0.5).  Call k runs the order
+    min(solver_order, k + 1), except that with lower_order_final and fewer than 15 timesteps the last call is first order and
+    (order 3) the last but one second order.
+    Every case is linear in (x, m0, m1, m2): step_row() encodes call k as [cx, ce, A, w0, w1, w2, slot_cur, slot1, slot2, push]
+    and the update kernel computes m = cx x + ce e, x' = A x + w0 m + w1 hist[slot1] + w2 hist[slot2], hist[slot_cur] = m
+    (a 3-deep ring of converted model outputs, fp32).  The scalars are computed in float64 from the fp32 alphas_cumprod (diffusers
+    keeps alpha / sigma / lambda as fp32 tensors: ~1e-7 relative apart)."""
+    kind = "dpm"
+    row_len = 10
+    diffusers_name = "DPMSolverMultistepScheduler"
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 beta_schedule: str = "scaled_linear", trained_betas=None, solver_order: int = 2,
+                 prediction_type: str = "epsilon", thresholding: bool = False, dynamic_thresholding_ratio: float = 0.995,
+                 sample_max_value: float = 1.0, algorithm_type: str = "dpmsolver++", solver_type: str = "midpoint",
+                 lower_order_final: bool = True, **unknown):
+        unknown = {k: v for k, v in unknown.items() if k not in _DPM_IGNORED_KEYS}
+        if unknown:
+            raise NotImplementedError(f"{type(self).__name__}: unsupported scheduler config keys {sorted(unknown)}")
+        if thresholding:
+            raise NotImplementedError("thresholding=True (dynamic thresholding) is not on the StoryGen path")
+        if solver_order not in (1, 2, 3):
+            raise NotImplementedError(f"solver_order={solver_order!r}: DPMSolverMultistepScheduler implements orders 1, 2 and 3")
+        if algorithm_type not in ("dpmsolver++", "dpmsolver"):
+            raise NotImplementedError(f"algorithm_type={algorithm_type!r}: only dpmsolver++ and dpmsolver exist")
+        if solver_type not in ("midpoint", "heun"):
+            raise NotImplementedError(f"solver_type={solver_type!r}: only midpoint and heun exist")
+        super().__init__(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                         beta_schedule=beta_schedule, trained_betas=trained_betas, prediction_type=prediction_type)
+        self.solver_order, self.algorithm_type, self.solver_type = int(solver_order), algorithm_type, solver_type
+        self.lower_order_final = bool(lower_order_final)
+        self._config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                            beta_schedule=beta_schedule, trained_betas=self._config["trained_betas"], solver_order=int(solver_order),
+                            prediction_type=prediction_type, thresholding=False,
+                            dynamic_thresholding_ratio=float(dynamic_thresholding_ratio), sample_max_value=float(sample_max_value),
+                            algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=bool(lower_order_final))
+
+    @classmethod
+    def from_config(cls, config, **kwargs) -> "DPMSolverMultistepSchedule":
+        """The diffusers idiom `DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)`: a dict-like config of this or
+        a DDIM / PNDM scheduler (their DDIM-only keys are ignored); keyword arguments override its entries."""
+        cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
+        cfg.update(kwargs)
+        return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
+
+    def timesteps(self, n: int) -> List[int]:
+        import numpy as np          # numpy's linspace + round-half-to-even, exactly as `set_timesteps` computes them
+        T = self.num_train_timesteps
+        return [int(t) for t in np.linspace(0, T - 1, n + 1).round()[::-1][:-1].astype(np.int64)]
+
+    def _als(self, t: int):
+        """(alpha, sigma, lambda) of timestep t in float64 from the fp32 alphas_cumprod."""
+        a = float(self.alphas_cumprod[t])
+        alpha, sigma = math.sqrt(a), math.sqrt(1.0 - a)
+        return alpha, sigma, math.log(alpha) - math.log(sigma)
+
+    def order_at(self, k: int, n_ts: int) -> int:
+        """The order of call k of a loop over n_ts timesteps (diffusers' lower_order_nums / lower_order_final logic)."""
+        lof = self.lower_order_final and n_ts < 15
+        if self.solver_order == 1 or k == 0 or (lof and k == n_ts - 1):
+            return 1
+        if self.solver_order == 2 or k == 1 or (lof and k == n_ts - 2):
+            return 2
+        return 3
+
+    def step_row(self, k: int, ts: List[int], n: int) -> List[float]:
+        T = len(ts)
+        s0 = int(ts[k])
+        t = int(ts[k + 1]) if k + 1 < T else 0
+        al_t, sg_t, lam_t = self._als(t)
+        al_0, sg_0, lam_0 = self._als(s0)
+        h = lam_t - lam_0
+        if self.algorithm_type == "dpmsolver++":
+            cx, ce = 1.0 / al_0, -sg_0 / al_0
+            A = sg_t / sg_0
+            em = math.expm1(-h)                                  # e^-h - 1
+            c = -al_t * em
+            b_heun = al_t * (em / h + 1.0)
+            d = -al_t * ((em + h) / (h * h) - 0.5)
+        else:
+            cx, ce = 0.0, 1.0
+            A = al_t / al_0
+            ep = math.expm1(h)                                   # e^h - 1
+            c = -sg_t * ep
+            b_heun = -sg_t * (ep / h - 1.0)
+            d = -sg_t * ((ep - h) / (h * h) - 0.5)
+        order = self.order_at(k, T)
+        w = [c, 0.0, 0.0]
+        if order == 2:
+            r0 = (lam_0 - self._als(int(ts[k - 1]))[2]) / h
+            b = 0.5 * c if self.solver_type == "midpoint" else b_heun
+            w = [c + b / r0, -b / r0, 0.0]
+        elif order == 3:
+            lam_1, lam_2 = self._als(int(ts[k - 1]))[2], self._als(int(ts[k - 2]))[2]
+            r0, r1 = (lam_0 - lam_1) / h, (lam_1 - lam_2) / h
+            b = b_heun                                           # the third-order update has no midpoint form
+            g = (b * r0 + d) / (r0 + r1)                         # weight of D1_0 - D1_1 in b D1 + d D2
+            w = [c + b / r0 + g / r0, -b / r0 - g * (1.0 / r0 + 1.0 / r1), g / r1]
+        cur = k % 3                                              # ring slot of m0; m1 / m2 sit one / two slots back
+        return [cx, ce, A, *w, float(cur), float((k - 1) % 3), float((k - 2) % 3), 1.0]
+
+
 def schedule_from_config(cfg, class_name: str = "") -> DDIMSchedule:
-    """A diffusers scheduler `.config` (dict, FrozenDict or attribute object) -> DDIMSchedule / PNDMSchedule; raises
-    NotImplementedError for every other scheduler class instead of silently running DDIM."""
+    """A diffusers scheduler `.config` (dict, FrozenDict or attribute object) -> DDIMSchedule / PNDMSchedule /
+    DPMSolverMultistepSchedule; raises NotImplementedError for every other scheduler class instead of silently running DDIM.
+    Euler, EulerAncestral and LMS stay out: their add_noise looks the reference pass's timestep (t / 10, pipeline.py:414-424) up
+    in their own timestep table, where it never is, so they cannot run the context stages."""
     def get(k, default=None):
         if isinstance(cfg, dict):
             return cfg.get(k, default)
@@ -190,10 +320,16 @@ def schedule_from_config(cfg, class_name: str = "") -> DDIMSchedule:
     keys = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "steps_offset", "set_alpha_to_one", "clip_sample",
             "trained_betas", "prediction_type", "skip_prk_steps")
     kw = {k: get(k) for k in keys if get(k) is not None}
+    if name in ("DPMSolverMultistepScheduler", "DPMSolverMultistepSchedule"):
+        dpm_keys = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "trained_betas", "solver_order",
+                    "prediction_type", "thresholding", "dynamic_thresholding_ratio", "sample_max_value", "algorithm_type",
+                    "solver_type", "lower_order_final")
+        return DPMSolverMultistepSchedule(**{k: get(k) for k in dpm_keys if get(k) is not None})
     if "PNDM" in name:
         kw.pop("clip_sample", None)
         return PNDMSchedule(**kw)
     if "DDIM" in name or name in ("", "DDIMSchedule"):
         kw.pop("skip_prk_steps", None)
         return DDIMSchedule(**kw)
-    raise NotImplementedError(f"scheduler {name!r}: the HIP loop implements DDIM (eta = 0) and PNDM/PLMS (skip_prk_steps)")
+    raise NotImplementedError(f"scheduler {name!r}: the HIP loop implements DDIM (eta = 0), PNDM/PLMS (skip_prk_steps) and "
+                              "DPMSolverMultistepScheduler (DPM-Solver / DPM-Solver++)")
