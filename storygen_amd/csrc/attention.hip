@@ -92,8 +92,10 @@ static int attn_fwd(const sg_attn_desc* d, float* lse2, sg_stream_t stream) {
         else if (big && prio) launch_attn<40, 4, 3, 1, true>(p, st);
         else if (big && opt.attn_d40_general) launch_attn<40, 4, 3, 1, false, false, false, true>(p, st);   // round-3 softmax (A/B)
         else if (big && opt.attn_lean) launch_attn<40, 4, 3, 1, false, false, true>(p, st);   // V^T fragments per k-step: fewer VGPRs
-        else if (big) launch_attn<40, 4, 3>(p, st);
-        else launch_attn<40, 2, 2>(p, st);
+        // round 7: tile 0 / branch-free steady state / drain (attn_d40_body, bit-identical); option attn_d40_loop = 1: the shared body
+        else if (opt.attn_d40_loop == 1) big ? launch_attn<40, 4, 3>(p, st) : launch_attn<40, 2, 2>(p, st);
+        else if (big) launch_attn_d40<4, 3>(p, st);
+        else launch_attn_d40<2, 2>(p, st);
     }
     else if (d->D == 80) {
         // measured (tools/bench_norm.py --attn, B3 Nq1024 Nk3072): 2 waves x 2 stages 76.6 us, 2 x 3 59.8, 4 x 3 55.2 — the
@@ -134,7 +136,8 @@ extern "C" int sg_attn_fwd_pair_f16(const sg_attn_desc* d0, const sg_attn_desc* 
     if (int rc = attn_params(d1, p1, "sg_attn_fwd_pair_f16[1]")) return rc;
     const SgOptions& opt = sg_options();
     const bool same = d0->D == d1->D && d0->B == d1->B && d0->H == d1->H && d0->Nq == d1->Nq;   // (short K/V rows: either problem)
-    const bool defaults = !opt.attn_sub2 && !opt.attn_prio && opt.attn_d80 == 1 && opt.attn_d160 >= 3;
+    const bool defaults = !opt.attn_sub2 && !opt.attn_prio && opt.attn_d80 == 1 && opt.attn_d160 >= 3 &&
+                          !(d0->D == 40 && opt.attn_d40_loop == 1);
     if (!same || !defaults) {
         if (int rc = attn_fwd(d0, nullptr, stream)) return rc;
         return attn_fwd(d1, nullptr, stream);
@@ -143,8 +146,8 @@ extern "C" int sg_attn_fwd_pair_f16(const sg_attn_desc* d0, const sg_attn_desc* 
     const AttnParams& b = p0.Nk >= p1.Nk ? p1 : p0;
     hipStream_t st = (hipStream_t)stream;
     if (d0->D == 40) {
-        if (attn_big(d0)) launch_attn_pair<40, 4, 3>(a, b, st);
-        else launch_attn_pair<40, 2, 2>(a, b, st);
+        if (attn_big(d0)) launch_attn_d40_pair<4, 3>(a, b, st);
+        else launch_attn_d40_pair<2, 2>(a, b, st);
     } else if (d0->D == 80) launch_attn_pair<80, 4, 3>(a, b, st);
     else launch_attn_pair<160, 4, 3>(a, b, st);
     SG_CHECK_LAUNCH("sg_attn_fwd_pair_f16");

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace sgattn {
 
@@ -503,6 +504,331 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, char* smem, c
                 }
             }
     }
+}
+
+// D = 40 inference forward (round 7): the fast path of attn_fwd_body (F40: same LDS layout, same MFMAs on the same operands, same exp2 and
+// rescale decisions — bit-identical results) with the tile loop cut into
+//   prologue      constants, Q fragments, ring fill, TILE 0 (sets the maximum: no ballot, no accumulator rescale);
+//   steady state  full tiles whose refill is a full tile too: no key mask, no first-tile selects, no tail / end-of-keys tests, the ring
+//                 stage a compile-time constant (S copies per trip) and the DMA sources three running wave-uniform pointers;
+//   drain         the last S .. 2S - 1 tiles with the tests the old loop made on every tile (ragged tail: mask + clamped DMA).
+// DMA pieces (1 KiB each, 5 of K and 5 of V^T per tile): wave w issues K segments j NW + w, V^T segments j NW + w (j < 4 / NW) — a property of
+// the piece index, not of the wave — and waves 0 / 1 one more: K segment 4 / V^T segment 4, through ONE pointer that was selected before
+// the loop.  The loop exists twice, for the waves with and without that last piece (NW = 4: waves 2, 3 have none), so that neither the
+// piece nor the counted wait behind it is predicated per tile.  attn_fwd_body selected K or V^T per piece and tile (segment i NW + w).
+template <int NW, int S>
+__device__ __forceinline__ void attn_d40_body(const AttnParams& p, char* smem, const int block, const int nblocks) {
+    constexpr int D = 40, DC = D / 8, NDK = 3, DT = 2, KROW = D * 2;
+    constexpr int K_BYTES = KVBLK * KROW, V_BYTES = D * 128;
+    constexpr int K_SEG = K_BYTES / 1024, V_SEG = V_BYTES / 1024;
+    constexpr int TSTAGE = K_BYTES + V_BYTES + F40_ONES, RING0 = F40_KPAD;
+    constexpr int NPAIR = (K_SEG - 1) / NW;     // (K, V^T) segment pairs per wave and tile
+    static_assert((NW == 2 || NW == 4) && (S == 2 || S == 3), "2 or 4 waves, 2 or 3 stages");
+    static_assert(K_SEG == 5 && V_SEG == 5 && NPAIR * NW == 4, "4 segments of K and of V^T over the waves + one of each for waves 0 and 1");
+    static_assert(RING0 + S * TSTAGE <= attn_smem_bytes<D, S, 1>(), "LDS size");
+
+    const int t = threadIdx.x, lane = t & 63, l31 = lane & 31, hi = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int work = xcd_remap(block, nblocks);          // head-major over the XCDs: see attn_fwd_body
+    const int bh = work / p.nqb, qb = work - bh * p.nqb;
+    const int h = bh / p.B, b = bh - h * p.B;
+    const int kvb = b < p.kv_batches ? b : b - (p.B - p.kv_batches);
+    const bool short_row = kvb < p.kv2;
+    const int Nk = short_row ? p.Nk2 : p.Nk;
+    const int q0 = (qb * NW + wave) * 32;
+    const f16* Q = p.q + (long)b * p.bsq + (long)h * D;
+    const f16* K = (short_row ? p.k2 + (long)kvb * p.bsk2 : p.k + (long)(kvb - p.kv2) * p.bsk) + (long)h * D;
+    const f16* VT = (short_row ? p.vt2 + (long)kvb * p.bsvt2 : p.vt + (long)(kvb - p.kv2) * p.bsvt) + (long)h * D * p.ldvt;
+    const int nkp8 = (Nk + 7) & ~7;
+    const int ntiles = (Nk + KVBLK - 1) / KVBLK, nfull = Nk / KVBLK;
+    const int ldk = (int)p.ldk, ldvt = (int)p.ldvt;
+
+    // the fast path's LDS constants (see F40_KPAD): written once, published by the first ring barrier
+    if (t < 8) {
+        const unsigned v = (t & 3) == 0 ? 0x3C003C00u : 0u;
+        *reinterpret_cast<unsigned*>(smem + ((t >> 2) ? 32 * KROW : 0) + 4 * (t & 3)) = v;
+    }
+    for (int i = t; i < S * (F40_ONES / 4); i += 64 * NW) {
+        const int img = i / (F40_ONES / 4), w = i - img * (F40_ONES / 4);
+        *reinterpret_cast<unsigned*>(smem + RING0 + img * TSTAGE + K_BYTES + V_BYTES + 4 * w) = 0x3C003C00u;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+    // ---- this lane's source coordinates in a K / V^T segment: (key within the tile, chunk * 8) / (d * ldvt, swizzled key chunk * 8)
+    auto kcoord = [&](int seg, int& row, int& col) __attribute__((always_inline)) {
+        const int s = seg * 64 + lane;
+        row = s / DC;
+        col = (s - row * DC) * 8;
+    };
+    auto vcoord = [&](int seg, int& row, int& col) __attribute__((always_inline)) {
+        const int s = seg * 64 + lane;
+        const int d = s >> 3, cs = s & 7;
+        row = d * ldvt;
+        col = (cs ^ ((d >> 1) & 7)) * 8;
+    };
+    unsigned koff[NPAIR], voff[NPAIR], xoff;    // 32-bit element offsets from the (wave-uniform) tile origins
+    {
+        int row, col;
+#pragma unroll
+        for (int j = 0; j < NPAIR; ++j) {
+            kcoord(j * NW + wave, row, col);
+            koff[j] = (unsigned)(row * ldk + col);
+            vcoord(j * NW + wave, row, col);
+            voff[j] = (unsigned)(row + col);
+        }
+        kcoord(K_SEG - 1, row, col);
+        const unsigned xk = (unsigned)(row * ldk + col);
+        vcoord(V_SEG - 1, row, col);
+        xoff = wave == 0 ? xk : (unsigned)(row + col);
+    }
+    const int xdst = wave == 0 ? (K_SEG - 1) * 1024 : K_BYTES + (V_SEG - 1) * 1024;      // LDS image offset of the last piece
+
+    // a full tile from its (wave-uniform) origins: Xt = Kt for wave 0, Vt for wave 1
+    auto issue_full = [&](auto has3, const f16* Kt, const f16* Vt, const f16* Xt, char* base) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < NPAIR; ++j) glds16(Kt + koff[j], base + (j * NW + wave) * 1024);
+#pragma unroll
+        for (int j = 0; j < NPAIR; ++j) glds16(Vt + voff[j], base + K_BYTES + (j * NW + wave) * 1024);
+        if constexpr (decltype(has3)::value) glds16(Xt + xoff, base + xdst);
+    };
+    // any tile (ring fill, drain): the ragged last tile clamps its keys (duplicates of the last valid row / chunk: finite, masked)
+    auto issue_any = [&](auto has3, int tile, char* base) __attribute__((always_inline)) {
+        const int key0 = tile * KVBLK;
+        if (key0 + KVBLK <= Nk) {
+            const f16* Kt = K + (long)key0 * ldk;
+            const f16* Vt = VT + key0;
+            issue_full(has3, Kt, Vt, wave == 0 ? Kt : Vt, base);
+        } else {
+            auto ktail = [&](int seg) __attribute__((always_inline)) {
+                int row, col;
+                kcoord(seg, row, col);
+                glds16(K + (long)min(key0 + row, Nk - 1) * ldk + col, base + seg * 1024);
+            };
+            auto vtail = [&](int seg) __attribute__((always_inline)) {
+                int row, col;
+                vcoord(seg, row, col);
+                glds16(VT + row + min(key0 + col, nkp8 - 8), base + K_BYTES + seg * 1024);
+            };
+#pragma unroll
+            for (int j = 0; j < NPAIR; ++j) ktail(j * NW + wave);
+#pragma unroll
+            for (int j = 0; j < NPAIR; ++j) vtail(j * NW + wave);
+            if constexpr (decltype(has3)::value) {
+                if (wave == 0) ktail(K_SEG - 1);
+                else vtail(V_SEG - 1);
+            }
+        }
+    };
+
+    // ---- Q^T fragments, pre-multiplied by scale * log2 e (see attn_fwd_body); settled before the ring's counted waits begin
+    f16x8 qf[NDK];
+    {
+        const int qi = min(q0 + l31, p.Nq - 1);
+#pragma unroll
+        for (int s = 0; s < NDK; ++s) {
+            const int d0 = s * 16 + hi * 8;
+            H8 x; x.u = make_uint4(0, 0, 0, 0);
+            if (d0 < D) x.u = ldg16(Q + (long)qi * p.ldq + d0);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x.h[j] = (f16)((float)x.h[j] * p.scale_log2);
+            qf[s] = x.v;
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+
+    f32x16 oacc[DT];
+#pragma unroll
+    for (int i = 0; i < DT; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[i][r] = 0.f;
+    float m_run = 0.f;        // what the Q^T pad slots subtract (fp16 hi + fp16 lo); tile 0 sets it
+
+    const int prow = (l31 & ~12) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);          // pi(l31): swap bits 2 and 3
+
+    // ---- one 64-key tile in ring stage STG.  FIRST: tile 0 (accumulators zero, m_run = 0 a placeholder); MASK: may be the ragged tile
+    auto compute = [&](auto first_, auto mask_, auto stage_, const int tile) __attribute__((always_inline)) {
+        constexpr bool FIRST = decltype(first_)::value, MASK = decltype(mask_)::value;
+        constexpr int STG = decltype(stage_)::value;
+        const char* sK = smem + RING0 + STG * TSTAGE;
+        const char* sV = sK + K_BYTES;
+        f32x16 s[2];
+        const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        f16x8 kf[2][NDK];
+        const char* k01 = sK + prow * KROW + hi * 16;
+        const char* k2 = hi ? smem : sK + prow * KROW + 64;     // contraction slots 40..47: the constant chunk
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            kf[kb][0] = *reinterpret_cast<const f16x8*>(k01 + kb * 32 * KROW);
+            kf[kb][1] = *reinterpret_cast<const f16x8*>(k01 + kb * 32 * KROW + 32);
+            kf[kb][2] = *reinterpret_cast<const f16x8*>(k2 + kb * 32 * KROW);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int st = 0; st < NDK; ++st)
+                s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[kb][st], qf[st], st == 0 ? zero16 : s[kb], 0, 0, 0);
+        f16x8 vf[4][DT];
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+            for (int i = 0; i < DT; ++i) {
+                const int d = min(i * 32 + l31, D);      // rows >= D: the row of ones (row sum)
+                vf[ks][i] = *reinterpret_cast<const f16x8*>(sV + d * 128 + (((ks * 2 + hi) ^ ((d >> 1) & 7)) << 4));
+            }
+        if constexpr (MASK) {
+            if ((tile + 1) * KVBLK > Nk) {
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int key = tile * KVBLK + kb * 32 + 16 * (r >> 3) + 8 * hi + (r & 7);
+                        if (key >= Nk) s[kb][r] = -INFINITY;
+                    }
+            }
+        }
+        float mx = s[0][0];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));          // finite: every tile holds >= 1 valid key
+        if (FIRST || __builtin_amdgcn_ballot_w64(mx > RESCALE_THR) != 0) {
+            float m_new = m_run + (FIRST ? mx : fmaxf(mx, 0.f));
+            m_new = fminf(fmaxf(m_new, -60000.f), 60000.f);
+            const f16 mh = (f16)m_new;
+            const f16 ml = (f16)(m_new - (float)mh);
+            m_new = (float)mh + (float)ml;                // what the pad slots will subtract, exactly
+            const float delta = m_new - m_run;
+            if constexpr (!FIRST) {
+                const float alpha = __builtin_amdgcn_exp2f(-delta);
+#pragma unroll
+                for (int i = 0; i < DT; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
+            }
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[kb][r] -= delta;
+            m_run = m_new;
+            if (hi) { qf[NDK - 1][0] = -mh; qf[NDK - 1][1] = -ml; }
+        }
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[kb][r] = __builtin_amdgcn_exp2f(s[kb][r]);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            f16x8 pf;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) pf[j] = (f16)s[ks >> 1][(ks & 1) * 8 + j];
+#pragma unroll
+            for (int i = 0; i < DT; ++i)
+                oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[ks][i], pf, oacc[i], 0, 0, 0);
+        }
+    };
+
+    char* const ring = smem + RING0;
+    auto run = [&](auto has3) __attribute__((always_inline)) {
+        constexpr int NP = 2 * NPAIR + (decltype(has3)::value ? 1 : 0);       // this wave's DMA pieces per tile
+        static_assert((S - 1) * NP < 64, "vmcnt is a 6-bit counter");
+        using T = std::true_type;
+        using F = std::false_type;
+        // invariant at the top of tile t: tiles t .. t + S - 2 (those that exist) have been issued; tile t lives in stage t % S
+#pragma unroll
+        for (int s = 0; s < S - 1; ++s)
+            if (s < ntiles) issue_any(has3, s, ring + s * TSTAGE);
+        if (S == 3 && 1 < ntiles) wait_vmcnt<NP>();
+        else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        if (S - 1 < ntiles) issue_any(has3, S - 1, ring + (S - 1) * TSTAGE);
+        compute(T{}, T{}, std::integral_constant<int, 0>{}, 0);
+
+        int tile = 1;
+        const long kstep = (long)KVBLK * ldk;
+        const f16* Kn = K + S * kstep;                  // origins of the next tile to issue (tile + S - 1)
+        const f16* Vn = VT + S * KVBLK;
+        const f16* Xn = wave == 0 ? Kn : Vn;
+        const long xstep = wave == 0 ? kstep : (long)KVBLK;
+        for (; tile + 2 * S - 2 < nfull; tile += S) {   // S tiles whose refills (up to tile + 2S - 2) are all full tiles
+            auto step = [&](auto stage_) __attribute__((always_inline)) {
+                constexpr int STG = decltype(stage_)::value;
+                wait_vmcnt<(S == 3 ? NP : 0)>();
+                __builtin_amdgcn_s_barrier();
+                issue_full(has3, Kn, Vn, Xn, ring + ((STG + S - 1) % S) * TSTAGE);
+                Kn += kstep; Vn += KVBLK; Xn += xstep;
+                compute(F{}, F{}, stage_, 0);
+            };
+            step(std::integral_constant<int, 1 % S>{});
+            step(std::integral_constant<int, 2 % S>{});
+            if constexpr (S == 3) step(std::integral_constant<int, 0>{});
+        }
+        for (; tile < ntiles; tile += S) {
+            auto step = [&](auto stage_, const int tl) __attribute__((always_inline)) {
+                constexpr int STG = decltype(stage_)::value;
+                if (tl < ntiles) {
+                    if (S == 3 && tl + 1 < ntiles) wait_vmcnt<NP>();
+                    else wait_vmcnt<0>();
+                    __builtin_amdgcn_s_barrier();
+                    if (tl + S - 1 < ntiles) issue_any(has3, tl + S - 1, ring + ((STG + S - 1) % S) * TSTAGE);
+                    compute(F{}, T{}, stage_, tl);
+                }
+            };
+            step(std::integral_constant<int, 1 % S>{}, tile);
+            step(std::integral_constant<int, 2 % S>{}, tile + 1);
+            if constexpr (S == 3) step(std::integral_constant<int, 0>{}, tile + 2);
+        }
+    };
+    if (NW == 4 && wave >= 2) run(std::false_type{});
+    else run(std::true_type{});
+
+    // ---- normalise and store: the row sum is O^T row 40 / 44, register 4 of the second tile in every lane
+    const float inv = 1.0f / oacc[DT - 1][4];
+    const int qi = q0 + l31;
+    if (qi < p.Nq) {
+        f16* O = p.o + (long)b * p.bso + (long)qi * p.ldo + (long)h * D;
+#pragma unroll
+        for (int i = 0; i < DT; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int d0 = i * 32 + 8 * g + 4 * hi;
+                if (d0 < D) {
+                    f16x4 w = {(f16)(oacc[i][4 * g + 0] * inv), (f16)(oacc[i][4 * g + 1] * inv),
+                               (f16)(oacc[i][4 * g + 2] * inv), (f16)(oacc[i][4 * g + 3] * inv)};
+                    *reinterpret_cast<f16x4*>(O + d0) = w;
+                }
+            }
+    }
+}
+
+template <int NW, int S>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) void attn_d40_kernel(const AttnParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<40, S, 1>()];
+    attn_d40_body<NW, S>(p, smem, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// the paired launch (attn_fwd_pair_kernel below) on the D = 40 body
+template <int NW, int S>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) void attn_d40_pair_kernel(const AttnParams a, const AttnParams b, const int na) {
+    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<40, S, 1>()];
+    if ((int)blockIdx.x < na) attn_d40_body<NW, S>(a, smem, (int)blockIdx.x, na);
+    else attn_d40_body<NW, S>(b, smem, (int)blockIdx.x - na, (int)gridDim.x - na);
+}
+
+template <int NW, int S>
+void launch_attn_d40(const AttnParams& p0, hipStream_t st) {
+    AttnParams p = p0;
+    p.nqb = sg_cdiv(p.Nq, 32 * NW);
+    hipLaunchKernelGGL((attn_d40_kernel<NW, S>), dim3(p.nqb * p.H * p.B), dim3(64 * NW), 0, st, p);
+}
+
+template <int NW, int S>
+void launch_attn_d40_pair(const AttnParams& a0, const AttnParams& b0, hipStream_t st) {
+    AttnParams a = a0, b = b0;
+    a.nqb = sg_cdiv(a.Nq, 32 * NW); b.nqb = sg_cdiv(b.Nq, 32 * NW);
+    const int na = a.nqb * a.H * a.B, nb = b.nqb * b.H * b.B;
+    hipLaunchKernelGGL((attn_d40_pair_kernel<NW, S>), dim3(na + nb), dim3(64 * NW), 0, st, a, b, na);
 }
 
 template <int D, int NW, int S, int SUB = 1, bool PRIO = false, bool LSE = false, bool LEAN = false, bool GENERAL = false>

@@ -50,6 +50,7 @@ struct SgOptions {
     int lat_wide = 0, lat_wide_m = 256;   // 1: M <= lat_wide_m (the 8x8 level) takes the 64x128-tile / 6-stage weight-streaming form (measured neutral: default off; tile hint (64, 128, 8) selects it per launch)
     int attn_sub2 = 0, attn_prio = 0, attn_d80 = 1, attn_d160 = 4 /* 4: key-split workgroups at Nq <= 256 */, attn_lean = 0;
     int attn_d40_general = 0;          // 1 = the D = 40 launches use the general softmax path (A/B against the padded-dimension fast path)
+    int attn_d40_loop = 0;             // 1 = the D = 40 inference launches run the shared tile loop of attn_fwd_body instead of attn_d40_body (A/B, bit-identical)
     int gn_no_fused = 0, gn_wide = 1;
     int gn_fused_nt = 1024;            // threads of the one-launch GroupNorm for slabs <= 16 384 values (256: the round-1 geometry; A/B)
     int gn_chunks = 0;                 // wide GroupNorm: cap on the row chunks per sample (0 = 256 / B, one round of workgroups; 64 = rounds 1-3)
