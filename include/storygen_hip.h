@@ -492,8 +492,9 @@ int     sg_adamw8bit(const sg_adamw_desc* d, sg_stream_t stream);
 /* ------------------------------------------------------------------------------------------------------------
  * Backward pass of the stage-2 training step (BASELINE config 4; /root/reference/train_StorySalon_stage2.py:322-327:
  * accelerator.backward(loss) through the main UNet pass, weight gradients for the attn3 modules only, :170-177).
- * STATUS: compiled for gfx950, not yet run on hardware (round 1's GPU budget was spent before they were written);
- * formulas and layer order are pinned on the CPU by oracle/storygen_backward.py + tests/test_oracle_backward.py.
+ * STATUS: validated on MI355X in round 2 (tests/test_backward_gpu.py); shape, stride and range edges in
+ * tests/test_attention_backward_edges_gpu.py and tests/test_backward_elementwise_edges_gpu.py.  Formulas and layer order are
+ * pinned on the CPU by oracle/storygen_backward.py + tests/test_oracle_backward.py.
  * The contractions reuse the forward entry points: linear dgrad = sg_gemm_f16 with the transposed weight, weight
  * gradient dW[n,k] = sum_m dy[m,n] x[m,k] = sg_gemm_f16(A = dy^T, W = x^T) on sg_transpose_f16 outputs, convolution
  * dgrad = sg_conv3x3_nhwc_f16 with the 180-degree-rotated, channel-swapped weight (stride 2: on sg_zero_stuff_f16's
@@ -545,7 +546,16 @@ int sg_attn_fwd_lse_f16(const sg_attn_desc* d, float* lse2, sg_stream_t stream);
  * kt (dq) and qt, dot (dkv) are the transposed copies ([B][H*D][N], row stride ld*t) the host gets from projection GEMMs
  * with swapped operands.  No K/V batch sharing (training has no CFG).  D in {40, 80, 160}; dkv needs Nq % 8 == 0; dq
  * accepts any Nk (text: 77) provided every kt row is finite up to Nk rounded up to 8 (ldkt >= that).
- * Text cross-attention (frozen K/V inputs and weights) needs only the dq call. */
+ * Text cross-attention (frozen K/V inputs and weights) needs only the dq call.
+ * What is read and written (pinned by tests/test_attention_backward_edges_gpu.py):
+ *   - transposed inputs are read in whole 16-byte chunks of the token axis: kt columns [Nk, Nk rounded up to 8) (and the same
+ *     columns of the forward's V^T) ARE read and must hold finite values — any finite value, they are multiplied by an exact
+ *     zero and do not change a bit of the result; Nq % 8 == 0 leaves qt / dot without such columns;
+ *   - nothing beyond N rounded up to 8 of a transposed row (ld*t may be larger), no token row beyond N of q / k / v / dout and no
+ *     column outside [h*D, (h+1)*D) of them is ever touched: that memory may hold NaN or belong to somebody else;
+ *   - dq is written in columns [0, H*D) of its Nq rows, dkt / dvt in columns [0, Nk) of their H*D rows, and nowhere else: the
+ *     outputs may be views of larger buffers (lddq > H*D, lddkt / lddvt > Nk, any batch stride);
+ *   - a descriptor that fails validation launches nothing. */
 typedef struct {
     const sg_half* q;    int64_t ldq, bsq;
     const sg_half* qt;   int64_t ldqt, bsqt;     /* dkv only */

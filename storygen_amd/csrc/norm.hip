@@ -436,28 +436,45 @@ struct GnBwdParams {
     f16* out16; long ldo16; int pad_w;   // ... or fp16 output (pad_w > 0: interior of [B, H+2, pad_w+2, C])
 };
 
-// mean / rstd of every group of batch b from the forward statistics partials (same code as gn_apply_wide_kernel's prologue)
+// mean / rstd of every group of batch b from the forward statistics partials.  The partials are sums of (x - pivot) and (x - pivot)^2 per
+// chunk; they are merged Chan-style (mean first, then the non-negative terms M2_c + n_c (mean_c - mean)^2 about it), not as q / n - md^2:
+// with the pivot pixel itself an outlier every other value sits far from it and the one subtraction of two fp32 sums over the whole
+// image cost 3 of fp32's 7 digits (30 sigma: 1.05e-4 on dx; tests/test_backward_elementwise_edges_gpu.py, pivot_outlier).  Per chunk the
+// same cancellation is left, but its rounding errors are independent between the chunks and average out.
 __device__ __forceinline__ void gnw_group_stats(const GnParams& p, int b, long xb, float* s_mean, float* s_rstd, float* s_ps, float* s_pq) {
     const int t = threadIdx.x;
     const int parts = GNW_NT / p.G;
     const int grp = t % p.G, part = t / p.G;
-    float s = 0.f, q = 0.f;
+    const float n = (float)p.HW * (float)p.cpg;
+    float s = 0.f;
     if (part < parts)
-        for (int c = part; c < p.nchunks; c += parts) {
-            const float* w = p.ws + (((long)b * p.nchunks + c) * p.G + grp) * 2;
-            s += w[0]; q += w[1];
-        }
-    s_ps[t] = s; s_pq[t] = q;
+        for (int c = part; c < p.nchunks; c += parts) s += p.ws[(((long)b * p.nchunks + c) * p.G + grp) * 2];
+    s_ps[t] = s;
     __syncthreads();
     if (t < p.G) {
-        s = 0.f; q = 0.f;
-        for (int k = 0; k < parts; ++k) { s += s_ps[k * p.G + t]; q += s_pq[k * p.G + t]; }
-        const float n = (float)p.HW * (float)p.cpg;
+        s = 0.f;
+        for (int k = 0; k < parts; ++k) s += s_ps[k * p.G + t];
+        s_mean[t] = s / n;                                     // mean of x - pivot; the pivot is added below
+    }
+    __syncthreads();
+    float m2 = 0.f;
+    if (part < parts) {
+        const float md = s_mean[grp];
+        for (int c = part; c < p.nchunks; c += parts) {
+            const float* w = p.ws + (((long)b * p.nchunks + c) * p.G + grp) * 2;
+            const float nc = (float)(min(p.HW, (c + 1) * p.rows_per_chunk) - c * p.rows_per_chunk) * (float)p.cpg;
+            const float mc = w[0] / nc, dm = mc - md;
+            m2 += fmaxf(w[1] - w[0] * mc, 0.f) + nc * dm * dm;
+        }
+    }
+    s_pq[t] = m2;
+    __syncthreads();
+    if (t < p.G) {
+        m2 = 0.f;
+        for (int k = 0; k < parts; ++k) m2 += s_pq[k * p.G + t];
         const float piv = load1f(p.x, xb + t * p.cpg, p.x_f32);
-        const float md = s / n;
-        const float var = fmaxf(q / n - md * md, 0.f);
-        s_mean[t] = piv + md;
-        s_rstd[t] = rsqrtf(var + p.eps);
+        s_mean[t] = piv + s_mean[t];
+        s_rstd[t] = rsqrtf(m2 / n + p.eps);
     }
     __syncthreads();
 }
