@@ -397,6 +397,15 @@ int sg_add_noise_f32(const float* src, const float* noise, const float* coef, fl
                      int64_t n, sg_stream_t stream);
 int sg_cfg_ddim_step_f32(const float* eps3, float* latents, float* latents3, const float* coef, int32_t N,
                          int64_t n, sg_stream_t stream);
+/* sg_cfg_ddim_var_step_f32: sg_cfg_ddim_step_f32 with diffusers' eta > 0 and clip_sample (DDIMScheduler.step with
+ *     use_clipped_model_output=False, which the reference never sets: the direction term keeps the unclipped guided eps).
+ *     coef = {s_img, s_txt, sa, sb, sap, dir, std, clip} (8 floats): x0 = (x - sb*eps)/sa; if clip != 0: x0 = clamp(x0, -1, 1);
+ *     x <- sap*x0 + dir*eps; if std != 0: x += std*noise[i] (`noise` = N*n floats of variance noise).  dir = sqrt(1 - abar_prev -
+ *     std^2), std = eta*sqrt((1 - abar_prev)/(1 - abar_t)*(1 - abar_t/abar_prev)).  With std = 0 and clip = 0 the result equals
+ *     sg_cfg_ddim_step_f32's bit for bit.  `noise` may be NULL only when std == 0: a NULL `noise` makes the call read coef[6] back
+ *     (it synchronises `stream` and cannot be captured into a graph) and return SG_EINVAL otherwise. */
+int sg_cfg_ddim_var_step_f32(const float* eps3, float* latents, float* latents3, const float* noise, const float* coef, int32_t N,
+                             int64_t n, sg_stream_t stream);
 /* sg_cfg_plms_step_f32: the same guidance combine followed by the PNDM / PLMS update of diffusers' PNDMScheduler with
  *     skip_prk_steps (model/pipeline.py:7-16 accepts it, ckpt/stable-diffusion-v1-5/scheduler/scheduler_config.json names
  *     it; call site :461): coef = {s_img, s_txt, A, Bc, w0, w1, w2, w3, slot_cur, slot1, slot2, slot3, push, use_kept,

@@ -232,6 +232,30 @@ __global__ void cfg_ddim_kernel(const float* eps3, float* lat, float* lat3, cons
     }
 }
 
+// DDIM with eta > 0 and / or clip_sample (diffusers DDIMScheduler.step, use_clipped_model_output=False: the direction term keeps
+// the unclipped guided epsilon): coef = [s_img, s_txt, sa, sb, sap, dir, std, clip] (storygen_amd/scheduler.py::
+// DDIMSchedule.var_step_coef).  With std = 0 and clip = 0 this is cfg_ddim_kernel, expression for expression.
+__global__ void cfg_ddim_var_kernel(const float* eps3, float* lat, float* lat3, const float* noise, const float* coef, int N,
+                                    long n) {
+    const long total = (long)N * n;
+    const float s_img = coef[0], s_txt = coef[1], sa = coef[2], sb = coef[3], sap = coef[4], dir = coef[5], sd = coef[6];
+    const bool clip = coef[7] != 0.f;
+    // a null `noise` is refused by the host when std != 0 at launch; a replayed graph reads std from device memory, so the
+    // kernel checks the pointer itself as well
+    const bool add = sd != 0.f && noise != nullptr;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const float eu = eps3[i], ei = eps3[total + i], ea = eps3[2 * total + i];
+        const float eps = eu + s_img * (ei - eu) + s_txt * (ea - ei);
+        const float x = lat[i];
+        float x0 = (x - sb * eps) / sa;
+        if (clip) x0 = x0 < -1.f ? -1.f : (x0 > 1.f ? 1.f : x0);      // NaN passes through, as torch.clamp lets it
+        float xp = sap * x0 + dir * eps;
+        if (add) xp += sd * noise[i];
+        lat[i] = xp;
+        if (lat3) { lat3[i] = xp; lat3[total + i] = xp; lat3[2 * total + i] = xp; }
+    }
+}
+
 // PNDM / PLMS update (diffusers PNDMScheduler.step_plms + _get_prev_sample, skip_prk_steps): coef = [s_img, s_txt, A, Bc,
 // w0..w3, slot_cur, slot1..slot3, push, use_kept, keep] (storygen_amd/scheduler.py::PNDMSchedule.step_row).
 __global__ void cfg_plms_kernel(const float* eps3, float* lat, float* lat3, float* hist, float* kept, const float* coef, int N,
@@ -413,6 +437,28 @@ extern "C" int sg_cfg_ddim_step_f32(const float* eps3, float* latents, float* la
     hipLaunchKernelGGL(cfg_ddim_kernel, dim3((int)min((long)1024, (total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, eps3,
                        latents, latents3, coef, N, (long)n);
     SG_CHECK_LAUNCH("sg_cfg_ddim_step_f32");
+    return SG_OK;
+}
+
+extern "C" int sg_cfg_ddim_var_step_f32(const float* eps3, float* latents, float* latents3, const float* noise, const float* coef,
+                                        int32_t N, int64_t n, sg_stream_t stream) {
+    SG_REQUIRE(eps3 && latents && coef && N > 0 && n > 0, "sg_cfg_ddim_var_step: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (!noise) {
+        // std lives in device memory: without a noise tensor it is read back (this synchronises the stream, so a call without
+        // noise cannot be captured into a graph; the sampler always passes its noise buffer)
+        float sd = 0.f;
+        if (hipMemcpyAsync(&sd, coef + 6, sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) {
+            (void)hipGetLastError();
+            return sg_set_error(SG_EINVAL, "sg_cfg_ddim_var_step: coef[6] (std) cannot be read back to check a null noise pointer");
+        }
+        SG_REQUIRE(sd == 0.f, "sg_cfg_ddim_var_step: noise is null but std = %g", (double)sd);
+    }
+    const long total = (long)N * n;
+    hipLaunchKernelGGL(cfg_ddim_var_kernel, dim3((int)min((long)1024, (total + 255) / 256)), dim3(256), 0, st, eps3, latents,
+                       latents3, noise, coef, N, (long)n);
+    SG_CHECK_LAUNCH("sg_cfg_ddim_var_step_f32");
     return SG_OK;
 }
 

@@ -16,7 +16,8 @@ Deliberate differences from the reference, none of which changes latents:
     default, :7-16 accepts it); `scheduler` may be a storygen_amd.scheduler.DDIMSchedule / PNDMSchedule /
     DPMSolverMultistepSchedule or any object whose `.config` carries the diffusers keys (`_class_name` or the object's class name
     selects the rule).  Anything else (Euler, EulerAncestral, LMS — their add_noise cannot take the reference pass's t / 10 —,
-    v-prediction, clip_sample, thresholding) raises instead of silently running DDIM.
+    v-prediction, thresholding) raises instead of silently running DDIM.  DDIM takes `eta` and `clip_sample` as diffusers does
+    (sg_cfg_ddim_var_step_f32); the noise of eta > 0 is drawn before the loop, in the reference's order (`_variance_noise`).
 """
 from __future__ import annotations
 
@@ -185,6 +186,25 @@ class StableDiffusionPipeline:
             latents = latents.to(device)
         return latents
 
+    @staticmethod
+    def _variance_noise(latents, steps, generator):
+        """The noise DDIM's eta > 0 adds, drawn before the loop exactly as the reference's `scheduler.step(noise_pred, t, latents, eta=eta,
+        generator=generator)` (:461) would draw it step by step (diffusers 0.13.1 DDIMScheduler.step: one `randn_tensor` of the model
+        output's shape per step — with a list of generators one [1, 4, h, w] draw per generator, concatenated — on the generator's
+        device, in the latents' dtype): nothing else consumes `generator` after prepare_latents, so the values are the same.  One call
+        per step, not one [steps, ...] draw: a Philox generator gives different values for the two.  -> fp32-castable [steps, N, 4, h, w]
+        on the latents' device."""
+        shape, dev, dtype = tuple(latents.shape), latents.device, latents.dtype
+        out = []
+        for _ in range(steps):
+            if isinstance(generator, list):
+                out.append(torch.cat([torch.randn((1,) + shape[1:], generator=g, device=g.device, dtype=dtype).to(dev)
+                                      for g in generator]))
+            else:
+                gdev = generator.device if generator is not None else dev
+                out.append(torch.randn(shape, generator=generator, device=gdev, dtype=dtype).to(dev))
+        return torch.stack(out)
+
     def decode_latents(self, latents):                                                   # :198-205
         image = self.vae.decode(latents / 0.18215).sample
         image = (image / 2 + 0.5).clamp(0, 1)
@@ -212,8 +232,6 @@ class StableDiffusionPipeline:
         self.check_inputs(prompt, height, width, callback_steps)
         if stage not in STAGES:
             stage = "no"                          # the reference treats every other string like 'no' (:425-427,436-438,444-445)
-        if eta != 0.0:
-            raise NotImplementedError("eta != 0 (stochastic DDIM) is not on the StoryGen path")
         batch_size = 1 if isinstance(prompt, str) else len(prompt)
         device = self._execution_device
         if not guidance_scale > 1.0:
@@ -246,13 +264,19 @@ class StableDiffusionPipeline:
         # UNet evaluations is a multiple of 5 (DDIM, DPM-Solver: n steps -> n; PNDM: n + 1)
         evals = len(schedule.timesteps(num_inference_steps))
         G = 5 if (callback is None and stage in STAGES[:2] and evals % 5 == 0) else 1
-        key = (n, h, w, R, text.shape[1], id(wts), schedule.key(), G)
+        # eta reaches only a scheduler whose step takes it (prepare_extra_step_kwargs, :208-221): DDIM
+        eta = float(eta) if schedule.kind == "ddim" else 0.0
+        variance_noise = self._variance_noise(latents, evals, generator) if eta > 0 else None
+        key = (n, h, w, R, text.shape[1], id(wts), schedule.key(), G, eta, bool(getattr(schedule, "clip_sample", False)))
         if self._sampler is None or self._sampler_key != key:
             self._sampler = StoryGenSampler(self.unet._arch, None, device, n, h, w, R, text.shape[1], schedule=schedule, weights=wts,
                                             ref_ahead=G)
             self._sampler_key = key
         smp = self._sampler
-        smp.prepare(inputs, num_inference_steps, stage, guidance_scale, image_guidance_scale)
+        if eta > 0 or getattr(schedule, "clip_sample", False):
+            smp.prepare(inputs, num_inference_steps, stage, guidance_scale, image_guidance_scale, eta=eta, variance_noise=variance_noise)
+        else:
+            smp.prepare(inputs, num_inference_steps, stage, guidance_scale, image_guidance_scale)
         with self.progress_bar(total=len(smp.timesteps)) as bar:
             for i, t in enumerate(smp.timesteps):                                         # :411-469
                 smp.step(i)

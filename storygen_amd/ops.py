@@ -803,6 +803,25 @@ def cfg_ddim_step(eps3: torch.Tensor, latents: torch.Tensor, latents3: Optional[
     return latents
 
 
+def cfg_ddim_var_step(eps3: torch.Tensor, latents: torch.Tensor, latents3: Optional[torch.Tensor], noise: Optional[torch.Tensor],
+                      coef: torch.Tensor) -> torch.Tensor:
+    """Guidance combine + DDIM update with eta > 0 and / or clip_sample (sg_cfg_ddim_var_step_f32); noise fp32 like latents (None
+    only when std = coef[6] is 0: the library then reads it back to check), coef = the 2 guidance scales +
+    (*DDIMSchedule.var_step_coef, clip) (8 floats)."""
+    for n, t in (("eps3", eps3), ("latents", latents), ("coef", coef)):
+        _f32(t, n)
+    if coef.numel() != 8 or eps3.numel() != 3 * latents.numel():
+        raise ValueError("cfg_ddim_var_step: eps3 must hold 3 latents, coef 8 floats")
+    if latents3 is not None and (latents3.dtype != torch.float32 or latents3.numel() != 3 * latents.numel()):
+        raise ValueError("cfg_ddim_var_step: latents3 must be fp32 and hold 3 latents")
+    if noise is not None and (noise.dtype != torch.float32 or noise.numel() != latents.numel() or not noise.is_contiguous()):
+        raise ValueError("cfg_ddim_var_step: noise must be contiguous fp32 of the latents' size")
+    N = latents.shape[0]
+    check(lib.sg_cfg_ddim_var_step_f32(eps3.data_ptr(), latents.data_ptr(), _p(latents3), _p(noise), coef.data_ptr(), N,
+                                       latents[0].numel(), _stream()), "sg_cfg_ddim_var_step_f32")
+    return latents
+
+
 def cfg_plms_step(eps3: torch.Tensor, latents: torch.Tensor, latents3: Optional[torch.Tensor], history: torch.Tensor,
                   kept: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
     """Guidance combine + PNDM/PLMS update (sg_cfg_plms_step_f32); history fp32 [4, *latents.shape], kept like latents."""

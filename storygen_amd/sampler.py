@@ -147,6 +147,13 @@ class StoryGenSampler:
             self.kept_sample = torch.zeros(lat_shape, **f32)
         elif self.schedule.kind == "dpm":         # DPM-Solver: ring of the last 3 converted model outputs (fp32: x0 = (x - sigma e) / alpha)
             self.model_outputs = torch.zeros((3,) + lat_shape, **f32)
+        # DDIM with eta > 0 or clip_sample (prepare(eta=...)): the update kernel is sg_cfg_ddim_var_step_f32, a table row carries its
+        # six scalars, and the variance noise of step k is staged from `var_noise_all` [steps, N, 4, h, w] (filled by prepare()) into
+        # `var_noise` [G, N, 4, h, w] — the buffer the captured graphs read — beside the upload of the step's parameter row(s)
+        self.var = False
+        self.eta = 0.0
+        self.var_noise: Optional[torch.Tensor] = None
+        self.var_noise_all: Optional[torch.Tensor] = None
         self.table: Optional[torch.Tensor] = None
         self.num_steps = 0
         self.k = 0
@@ -221,7 +228,7 @@ class StoryGenSampler:
             self.ref, self.ctx_sets, self.kv_sets, self.plans = None, [], [], []
             self.side_main = torch.cuda.Stream(device=self.dev) if self.use_graph else None
             self.side_ref = None
-            self.n_par = self.B + 2 + self.schedule.row_len
+            self.n_par = self.B + 2 + self._row_len()
             self.params = torch.zeros(1, self.n_par, dtype=torch.float32, device=self.dev)
             self.lat_trace, self.group_direct = None, False
             self.layout, self.graph, self.graphs, self.g_ref, self.g_main, self.tails = key, None, [], [], [], {}
@@ -288,7 +295,7 @@ class StoryGenSampler:
         self.ref_noise = torch.zeros((self.U,) + tuple(self.latents.shape[1:]), **f32)
         # per-step parameters, one row per step of a group (G rows; only the group schedule reads rows > 0):
         # [U] ref timesteps | [B] main timestep | [U,2] add_noise coefs | guidance + update-rule coefs
-        self.n_par = 3 * self.U + self.B + 2 + self.schedule.row_len
+        self.n_par = 3 * self.U + self.B + 2 + self._row_len()
         self.params = torch.zeros(G if self.group else 1, self.n_par, **f32)
         self.lat_trace = torch.zeros((G,) + tuple(self.latents.shape), **f32) if self.group else None
         self.layout, self.graph, self.graphs, self.tails = key, None, [], {}
@@ -301,6 +308,10 @@ class StoryGenSampler:
                 self.main_stream = torch.cuda.Stream(device=self.dev, priority=-1)
             self.ev_ref = [torch.cuda.Event(), torch.cuda.Event()]      # "reference pass of a group of this parity is done"
 
+    def _row_len(self) -> int:
+        """Update-rule scalars per table row: the schedule's own, or (sa, sb, sap, dir, std, clip) on the eta / clip_sample path."""
+        return 6 if self.var else self.schedule.row_len
+
     def _par_views(self, row: int = 0):
         """(reference timesteps [U], main timesteps [B], add_noise coefficients [U, 2], guidance + update-rule scalars) of parameter
         row `row` (the group schedule keeps one row per step of the group; everything else uses row 0)."""
@@ -310,14 +321,25 @@ class StoryGenSampler:
 
     # ------------------------------------------------------------------------------------------------ setup
     def prepare(self, inputs: Dict[str, torch.Tensor], num_inference_steps: int = 50,
-                stage: str = "multi-image-condition", guidance_scale: float = 7.5, image_guidance_scale: float = 3.5):
+                stage: str = "multi-image-condition", guidance_scale: float = 7.5, image_guidance_scale: float = 3.5,
+                eta: float = 0.0, variance_noise: Optional[torch.Tensor] = None):
         """`inputs` as produced by storygen_amd.synth.synthetic_inputs / the pipeline's CLIP+VAE plumbing
         (pipeline.py:359-409): latents, image_prompts [R,N,..], zero_prompt, noise, text, uncond, prev_text,
-        prev_uncond."""
+        prev_uncond.  eta: diffusers' DDIM eta (pipeline.py:208-221,461 hands it to schedulers whose `step` takes it: DDIM only — PNDM
+        and DPM-Solver ignore it, as there); eta > 0 needs variance_noise, fp32 [steps, N, 4, h, w]: step k adds std_k *
+        variance_noise[k] (what `scheduler.step(..., generator=...)` draws, drawn by the caller)."""
         if stage not in STAGES:
             raise ValueError(f"stage must be one of {STAGES}")
         if guidance_scale <= 1.0:
             raise ValueError("only the classifier-free-guidance path of the reference loop works (SURVEY F6g)")
+        if not eta >= 0.0:
+            raise ValueError(f"eta = {eta!r}: diffusers' DDIM eta lies in [0, 1]")
+        ddim = self.schedule.kind == "ddim"
+        eta = float(eta) if ddim else 0.0
+        var = ddim and (eta > 0.0 or bool(getattr(self.schedule, "clip_sample", False)))
+        if var != self.var:                       # another update kernel and row length: parameter block and graphs are rebuilt
+            self.var, self.layout = var, None
+        self.eta = eta
         dev, N, R = self.dev, self.N, self.R
         pu = inputs["prev_uncond"]
         share_zero = (self.dedup and stage == "multi-image-condition"
@@ -326,7 +348,7 @@ class StoryGenSampler:
         # ---- the per-step table: host arithmetic only
         ts = self.schedule.timesteps(num_inference_steps)
         rows, row0 = step_table(self.schedule, ts, num_inference_steps, self.units[:self.U0], R, stage, self.B, self.G,
-                                self.ahead and not self.no_ctx, image_guidance_scale, guidance_scale)
+                                self.ahead and not self.no_ctx, image_guidance_scale, guidance_scale, eta=eta if self.var else None)
         if self.group and len(rows) % self.G:
             raise ValueError(f"ref_ahead = {self.G} runs the loop in groups of {self.G} UNet evaluations: {len(rows)} evaluations "
                              f"({num_inference_steps} inference steps) is not a multiple")
@@ -335,6 +357,8 @@ class StoryGenSampler:
         self.timesteps = ts
         self.num_steps = len(ts)                  # PNDM: n + 1 UNet evaluations for n inference steps
         self.k = 0
+        if self.var:
+            self._set_variance_noise(variance_noise)
         # ---- uploads.  The inputs are pageable host tensors, i.e. every .to(device) blocks the host until the stream reaches it: all of
         # them go first (few, batched — one stacked copy per kind instead of one per reference sample), nothing long is queued yet
         self.latents.copy_(inputs["latents"].to(dev, torch.float32) * self.schedule.init_noise_sigma)
@@ -375,6 +399,31 @@ class StoryGenSampler:
             self._tail_graph((last // self.G) % 2)
         if self.ahead and not self.no_ctx and not primed:
             self._prime()
+
+    def _set_variance_noise(self, variance_noise: Optional[torch.Tensor]):
+        """The eta / clip_sample path's noise buffers.  `var_noise` (what the graphs read) is allocated once per layout, so graphs
+        captured by an earlier prepare() stay valid; `var_noise_all` is refilled by every prepare() (zeros when eta = 0: std = 0
+        then, the kernel does not read it)."""
+        T, G = self.num_steps, self.G if self.group else 1
+        shape = tuple(self.latents.shape)
+        if self.var_noise is None:
+            self.var_noise = torch.zeros((G,) + shape, dtype=torch.float32, device=self.dev)
+        if self.var_noise_all is None or self.var_noise_all.shape[0] < T:
+            self.var_noise_all = torch.zeros((T,) + shape, dtype=torch.float32, device=self.dev)
+        if self.eta > 0.0:
+            if variance_noise is None:
+                raise ValueError("eta > 0 needs variance_noise [steps, N, 4, h, w] (the sampler draws nothing itself)")
+            if tuple(variance_noise.shape) != (T,) + shape:
+                raise ValueError(f"variance_noise has shape {tuple(variance_noise.shape)}, expected {(T,) + shape}")
+            self.var_noise_all[:T].copy_(variance_noise.to(self.dev, torch.float32))
+        else:
+            self.var_noise_all.zero_()
+
+    def _stage_variance_noise(self, k: int, count: int = 1):
+        """Variance noise of steps k .. k + count - 1 -> the rows of `var_noise` the update kernels of the next replay read (a
+        device-to-device copy on the current stream, ordered like the parameter upload it goes with)."""
+        if self.var:
+            self.var_noise[:count].copy_(self.var_noise_all[k:k + count], non_blocking=True)
 
     def _pinned(self, name: str, t: torch.Tensor) -> torch.Tensor:
         """t in a pinned host buffer kept across prepare() calls (a fresh pin_memory() allocation costs milliseconds per call)."""
@@ -418,7 +467,9 @@ class StoryGenSampler:
         main.x_in.copy_(self.latents3)                                                    # :448-453
         main.t_in.copy_(t_main)
         eps3 = main.forward(consume=not self.no_ctx, text_cache=True, side=self.side_main)
-        if self.schedule.kind == "plms":                                                  # :457-461
+        if self.var:                                                                      # :457-461, DDIM with eta / clip_sample
+            ops.cfg_ddim_var_step(eps3, self.latents, self.latents3, self.var_noise[row], cd)
+        elif self.schedule.kind == "plms":
             ops.cfg_plms_step(eps3, self.latents, self.latents3, self.eps_history, self.kept_sample, cd)
         elif self.schedule.kind == "dpm":
             ops.cfg_dpm_step(eps3, self.latents, self.latents3, self.model_outputs, cd)
@@ -561,6 +612,7 @@ class StoryGenSampler:
             G = self.G
             if k % G == 0:
                 self.params.copy_(self.table[k:k + G], non_blocking=True)
+                self._stage_variance_noise(k, G)
                 if self.graphs:
                     (self._tail_graph((k // G) % 2) if last else self.graphs[(k // G) % 2]).replay()
                 else:
@@ -568,6 +620,7 @@ class StoryGenSampler:
             self.k = k + 1
             return
         self.params.copy_(self.table[k], non_blocking=True)
+        self._stage_variance_noise(k)
         if self.graphs:
             (self._tail_graph(k % 2) if last else self.graphs[k % 2]).replay()
         elif self.graph is not None:
@@ -606,6 +659,7 @@ class StoryGenSampler:
         with torch.cuda.stream(cur):
             par[U:U + B].copy_(row[U:U + B], non_blocking=True)                           # main timestep
             par[3 * U + B:].copy_(row[3 * U + B:], non_blocking=True)                     # guidance + DDIM coefficients
+            self._stage_variance_noise(k)
             self.g_main[ctx_set_of_step(k, G)].replay()
         if cur is not caller:
             caller.wait_stream(cur)
@@ -666,11 +720,13 @@ def first_ctx_set_of_group(j: int, G: int) -> int:
 
 
 def step_table(schedule: DDIMSchedule, ts, num_inference_steps: int, units0, R: int, stage: str, B: int, G: int, overlap: bool,
-               image_guidance_scale: float, guidance_scale: float):
+               image_guidance_scale: float, guidance_scale: float, eta: Optional[float] = None):
     """The scalars every denoising step needs, as rows of the pinned table the sampler uploads from (pure host logic).
 
     Row k = [U reference timesteps | B main timesteps | U x 2 add_noise coefficients | 2 guidance scales + the update
     rule's scalars (schedule.step_row: 4 for DDIM, 13 for PNDM/PLMS, 10 for DPM-Solver)], U = G * len(units0).  units0 = the (kind, frame, sample) reference samples of ONE step.
+    eta (a number, DDIM only): the eta / clip_sample path — the rule's scalars are the 6 of sg_cfg_ddim_var_step_f32,
+    (*schedule.var_step_coef(t, n, eta), clip_sample); None (default) = the schedule's own row.
     Which reference scalars row k carries depends on the schedule of the passes:
       no overlap          : those of step k itself (reference pass, then main pass);
       overlap, G = 1      : those of step k+1 (graph k runs main pass k beside reference pass k+1);
@@ -679,6 +735,12 @@ def step_table(schedule: DDIMSchedule, ts, num_inference_steps: int, units0, R: 
     Steps past the end repeat the last timestep (their features are never consumed).  Also returns row0: the reference
     scalars of the very first pass / group (the one nothing overlaps with), main part zero."""
     T = len(ts)
+    row_len = schedule.row_len if eta is None else 6
+
+    def rule(k):
+        if eta is None:
+            return schedule.step_row(k, ts, num_inference_steps)
+        return [*schedule.var_step_coef(int(ts[k]), num_inference_steps, eta), float(schedule.clip_sample)]
 
     def ref_part(t):
         ref_t = int(t) // 10                                                              # pipeline.py:414-415
@@ -703,10 +765,10 @@ def step_table(schedule: DDIMSchedule, ts, num_inference_steps: int, units0, R: 
         else:
             tt, cc = ref_part(ts[min(k + 1, T - 1)] if overlap else t)
         row = tt + [float(t)] * B + cc
-        row += [image_guidance_scale, guidance_scale, *schedule.step_row(k, ts, num_inference_steps)]
+        row += [image_guidance_scale, guidance_scale, *rule(k)]
         rows.append(row)
     tt, cc = group_ref(0) if G > 1 else ref_part(ts[0])
-    return rows, tt + [float(ts[0])] * B + cc + [0.0] * (2 + schedule.row_len)
+    return rows, tt + [float(ts[0])] * B + cc + [0.0] * (2 + row_len)
 
 
 def gather_latents(latents: torch.Tensor) -> torch.Tensor:

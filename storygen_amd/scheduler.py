@@ -41,10 +41,10 @@ class DDIMSchedule:
                             beta_schedule=beta_schedule, steps_offset=steps_offset, set_alpha_to_one=set_alpha_to_one,
                             trained_betas=None if trained_betas is None else [float(b) for b in trained_betas],
                             prediction_type=prediction_type,
-                            # always False here (True raises below) and written out explicitly: diffusers' DDIMScheduler DEFAULTS
-                            # clip_sample to True, so a saved config without the key would make the reference's inference.py:48
+                            # written out explicitly: diffusers' DDIMScheduler DEFAULTS clip_sample to True, so a saved config
+                            # without the key would make the reference's inference.py:48
                             # (`DDIMScheduler.from_pretrained(ckpt, subfolder="scheduler")`) clip x0 on a checkpoint written here
-                            clip_sample=False)
+                            clip_sample=bool(clip_sample))
         if trained_betas is not None:
             betas = torch.tensor([float(b) for b in trained_betas], dtype=torch.float32)
             if betas.numel() != num_train_timesteps:
@@ -55,8 +55,8 @@ class DDIMSchedule:
             betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
         else:
             raise NotImplementedError(f"{beta_schedule} is not implemented for DDIMSchedule")
-        if clip_sample:
-            raise NotImplementedError("clip_sample=True is not on the StoryGen path")
+        # x0 clamped to [-1, 1] in every step (diffusers' DDIMScheduler default; PNDM / DPM-Solver have no such key and drop it)
+        self.clip_sample = bool(clip_sample)
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
         self.num_train_timesteps = num_train_timesteps
@@ -116,6 +116,24 @@ class DDIMSchedule:
             v = memo[(int(t), int(n))] = (float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_p ** 0.5), float((1 - a_p) ** 0.5))
         return v
 
+    def var_step_coef(self, t: int, n: int, eta: float):
+        """(sqrt(abar_t), sqrt(1-abar_t), sqrt(abar_prev), dir, std) for x_t -> x_{t - T/n} with diffusers' eta
+        (`DDIMScheduler.step` / `_get_variance`, the same fp32 tensor arithmetic): std = eta sqrt(variance), variance =
+        (1 - abar_prev) / (1 - abar_t) (1 - abar_t / abar_prev), dir = sqrt(1 - abar_prev - std^2).  eta = 0 gives step_coef(t, n)
+        and std = 0."""
+        memo = self.__dict__.setdefault("_var_step_coef_memo", {})
+        key = (int(t), int(n), float(eta))
+        v = memo.get(key)
+        if v is None:
+            prev = t - self.num_train_timesteps // n
+            a_t = self.alphas_cumprod[t]
+            a_p = self.alphas_cumprod[prev] if prev >= 0 else self.final_alpha_cumprod
+            variance = ((1 - a_p) / (1 - a_t)) * (1 - a_t / a_p)
+            std = float(eta) * variance ** 0.5
+            v = memo[key] = (float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_p ** 0.5), float((1 - a_p - std ** 2) ** 0.5),
+                             float(std))
+        return v
+
 
 class PNDMSchedule(DDIMSchedule):
     """diffusers 0.13.1 PNDMScheduler with skip_prk_steps=True (the SD-1.5 default): pseudo linear multistep (PLMS).
@@ -139,7 +157,7 @@ class PNDMSchedule(DDIMSchedule):
         if not skip_prk_steps:
             raise NotImplementedError("PNDM with Runge-Kutta warm-up steps (skip_prk_steps=false) is not on the StoryGen path; the "
                                       "shipped scheduler_config.json sets skip_prk_steps=true")
-        kw.pop("clip_sample", None)
+        kw.pop("clip_sample", None)                      # not a PNDMScheduler key: diffusers drops it the same way
         super().__init__(**kw)
         self._config["skip_prk_steps"] = True
         self._config.pop("set_alpha_to_one", None)
@@ -331,5 +349,5 @@ def schedule_from_config(cfg, class_name: str = "") -> DDIMSchedule:
     if "DDIM" in name or name in ("", "DDIMSchedule"):
         kw.pop("skip_prk_steps", None)
         return DDIMSchedule(**kw)
-    raise NotImplementedError(f"scheduler {name!r}: the HIP loop implements DDIM (eta = 0), PNDM/PLMS (skip_prk_steps) and "
+    raise NotImplementedError(f"scheduler {name!r}: the HIP loop implements DDIM (any eta, clip_sample), PNDM/PLMS (skip_prk_steps) and "
                               "DPMSolverMultistepScheduler (DPM-Solver / DPM-Solver++)")

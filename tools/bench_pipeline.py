@@ -4,8 +4,8 @@
 prompts, VAE encode of the prior frames, the denoising loop, VAE decode.  Random weights of the reference's configs (no checkpoints here),
 a stand-in tokenizer (token ids are irrelevant for timing).  Prints one JSON line; non-contract (bench.py is the contract).
 
-    python tools/bench_pipeline.py [STEPS] [--scheduler ddim|dpm]      one configuration (default: 40 DDIM steps)
-    python tools/bench_pipeline.py --compare ddim:40,ddim:50,dpm:20,dpm:25 [--rounds 5]
+    python tools/bench_pipeline.py [STEPS] [--scheduler ddim|dpm] [--eta E]     one configuration (default: 40 DDIM steps, eta 0)
+    python tools/bench_pipeline.py --compare ddim:40,ddim:50,dpm:20,dpm:25,ddim:40:0.5 [--rounds 5]      (a third field = eta)
         several configurations in one process (one pipeline each, sharing the networks), timed in alternation round by round so that
         drift of the machine spreads over all of them; one JSON line per configuration with every sample.
 dpm = DPM-Solver++(2M), diffusers' DPMSolverMultistepScheduler defaults (storygen_amd.scheduler.DPMSolverMultistepSchedule)."""
@@ -40,11 +40,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("steps", nargs="?", type=int, default=40)
     ap.add_argument("--scheduler", choices=sorted(SCHEDULERS), default="ddim")
-    ap.add_argument("--compare", default="", help="comma-separated scheduler:steps list, timed in alternation")
+    ap.add_argument("--eta", type=float, default=0.0, help="DDIM's eta (> 0: stochastic DDIM, the variance noise drawn from a seeded "
+                                                           "generator inside the timed call, as a user's call draws it)")
+    ap.add_argument("--compare", default="", help="comma-separated scheduler:steps[:eta] list, timed in alternation")
     ap.add_argument("--rounds", type=int, default=3, help="timed calls per configuration")
     args = ap.parse_args()
-    configs = [(c.split(":")[0], int(c.split(":")[1])) for c in args.compare.split(",")] if args.compare else [(args.scheduler, args.steps)]
-    for name, _ in configs:
+    def parse(c):
+        f = c.split(":")
+        return f[0], int(f[1]), float(f[2]) if len(f) > 2 else 0.0
+    configs = [parse(c) for c in args.compare.split(",")] if args.compare else [(args.scheduler, args.steps, args.eta)]
+    for name, _, _ in configs:
         if name not in SCHEDULERS:
             raise SystemExit(f"unknown scheduler {name!r} (choose from {sorted(SCHEDULERS)})")
     dev, f16 = torch.device("cuda:0"), torch.float16
@@ -54,7 +59,7 @@ def main():
     clip = CLIPTextModel(dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12)).to(dev, f16)
     frames = torch.rand(1, 3, 3, 512, 512)
     pipes = []
-    for name, steps in configs:             # one pipeline (hence one cached sampler and its graphs) per configuration
+    for name, steps, _ in configs:          # one pipeline (hence one cached sampler and its graphs) per configuration
         pipe = StableDiffusionPipeline(vae=vae, text_encoder=clip, tokenizer=Tok(), unet=unet, scheduler=SCHEDULERS[name][1]())
         pipe.set_progress_bar_config(disable=True)
         pipes.append(pipe)
@@ -62,6 +67,7 @@ def main():
     def call(i):
         return pipes[i](stage="multi-image-condition", prompt="a", image_prompt=frames, prev_prompt=["b", "c", "d"], height=512,
                         width=512, num_inference_steps=configs[i][1], guidance_scale=7.0, image_guidance_scale=3.5,
+                        eta=configs[i][2], generator=torch.Generator(device=dev).manual_seed(0) if configs[i][2] > 0 else None,
                         output_type="np").images
 
     imgs = []
@@ -75,12 +81,12 @@ def main():
             imgs[i] = call(i)
             torch.cuda.synchronize()
             ts[i].append(time.perf_counter() - t0)
-    for (name, steps), samples, img in zip(configs, ts, imgs):
+    for (name, steps, eta), samples, img in zip(configs, ts, imgs):
         srt = sorted(samples)
         med = srt[len(srt) // 2]
         print(json.dumps({"workload": f"one pipeline call: {steps} {SCHEDULERS[name][0]} steps, 512x512, 3 prior frames, CFG, HIP CLIP + "
                                       "VAE + UNet, fp16",
-                          "scheduler": name, "steps": steps, "seconds_per_image_median": round(med, 4), "seconds_min": round(srt[0], 4),
+                          "scheduler": name, "steps": steps, "eta": eta, "seconds_per_image_median": round(med, 4), "seconds_min": round(srt[0], 4),
                           "seconds_max": round(srt[-1], 4), "seconds_all": [round(v, 4) for v in samples],
                           "ms_per_step_incl_everything": round(med / steps * 1e3, 2), "image_shape": list(img.shape),
                           "finite": bool(torch.isfinite(torch.as_tensor(img)).all())}))
