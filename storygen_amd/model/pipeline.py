@@ -264,19 +264,17 @@ class StableDiffusionPipeline:
         # UNet evaluations is a multiple of 5 (DDIM, DPM-Solver: n steps -> n; PNDM: n + 1)
         evals = len(schedule.timesteps(num_inference_steps))
         G = 5 if (callback is None and stage in STAGES[:2] and evals % 5 == 0) else 1
-        # eta reaches only a scheduler whose step takes it (prepare_extra_step_kwargs, :208-221): DDIM
-        eta = float(eta) if schedule.kind == "ddim" else 0.0
-        variance_noise = self._variance_noise(latents, evals, generator) if eta > 0 else None
-        key = (n, h, w, R, text.shape[1], id(wts), schedule.key(), G, eta, bool(getattr(schedule, "clip_sample", False)))
+        # eta reaches only a scheduler whose step takes it (prepare_extra_step_kwargs, :208-221): the rule of any other has eta = 0
+        rule = schedule.update_rule(float(eta))
+        eta = rule.eta
+        variance_noise = self._variance_noise(latents, evals, generator) if rule.needs_noise and eta > 0 else None
+        key = (n, h, w, R, text.shape[1], id(wts), schedule.key(), G, eta, rule.key)
         if self._sampler is None or self._sampler_key != key:
             self._sampler = StoryGenSampler(self.unet._arch, None, device, n, h, w, R, text.shape[1], schedule=schedule, weights=wts,
                                             ref_ahead=G)
             self._sampler_key = key
         smp = self._sampler
-        if eta > 0 or getattr(schedule, "clip_sample", False):
-            smp.prepare(inputs, num_inference_steps, stage, guidance_scale, image_guidance_scale, eta=eta, variance_noise=variance_noise)
-        else:
-            smp.prepare(inputs, num_inference_steps, stage, guidance_scale, image_guidance_scale)
+        smp.prepare(inputs, num_inference_steps, stage, guidance_scale, image_guidance_scale, eta=eta, variance_noise=variance_noise)
         with self.progress_bar(total=len(smp.timesteps)) as bar:
             for i, t in enumerate(smp.timesteps):                                         # :411-469
                 smp.step(i)

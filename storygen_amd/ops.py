@@ -794,13 +794,26 @@ def add_noise(src: torch.Tensor, noise: torch.Tensor, coef: torch.Tensor, out: t
     return out
 
 
+def _cfg_step(fn_name: str, eps3: torch.Tensor, latents: torch.Tensor, latents3: Optional[torch.Tensor], coef: torch.Tensor,
+              n_coef: int, *extra: Optional[torch.Tensor]) -> torch.Tensor:
+    """The checks and the call every update rule shares: sg_<fn_name>_f32(eps3, latents, latents3, *extra, coef, N, n, stream) with
+    eps3 = 3 latents, latents3 = None or 3 latents, coef = the 2 guidance scales + the rule's row (n_coef floats), all fp32."""
+    for n, t in (("eps3", eps3), ("latents", latents), ("coef", coef)):
+        _f32(t, n)
+    if eps3.numel() != 3 * latents.numel() or coef.numel() != n_coef:
+        raise ValueError(f"{fn_name}: eps3 must hold 3 latents, coef {n_coef} floats")
+    if latents3 is not None and (latents3.dtype != torch.float32 or latents3.numel() != 3 * latents.numel()):
+        raise ValueError(f"{fn_name}: latents3 must be fp32 and hold 3 latents")
+    name = f"sg_{fn_name}_f32"
+    check(getattr(lib, name)(eps3.data_ptr(), latents.data_ptr(), _p(latents3), *map(_p, extra), coef.data_ptr(), latents.shape[0],
+                             latents[0].numel(), _stream()), name)
+    return latents
+
+
 def cfg_ddim_step(eps3: torch.Tensor, latents: torch.Tensor, latents3: Optional[torch.Tensor], coef: torch.Tensor
                   ) -> torch.Tensor:
-    _f32(eps3, "eps3"), _f32(latents, "latents"), _f32(coef, "coef")
-    N = latents.shape[0]
-    check(lib.sg_cfg_ddim_step_f32(eps3.data_ptr(), latents.data_ptr(), _p(latents3), coef.data_ptr(), N,
-                                   latents[0].numel(), _stream()), "sg_cfg_ddim_step_f32")
-    return latents
+    """Guidance combine + DDIM update, eta = 0 (sg_cfg_ddim_step_f32); coef = the 2 guidance scales + DDIMSchedule.step_coef."""
+    return _cfg_step("cfg_ddim_step", eps3, latents, latents3, coef, 6)
 
 
 def cfg_ddim_var_step(eps3: torch.Tensor, latents: torch.Tensor, latents3: Optional[torch.Tensor], noise: Optional[torch.Tensor],
@@ -808,47 +821,29 @@ def cfg_ddim_var_step(eps3: torch.Tensor, latents: torch.Tensor, latents3: Optio
     """Guidance combine + DDIM update with eta > 0 and / or clip_sample (sg_cfg_ddim_var_step_f32); noise fp32 like latents (None
     only when std = coef[6] is 0: the library then reads it back to check), coef = the 2 guidance scales +
     (*DDIMSchedule.var_step_coef, clip) (8 floats)."""
-    for n, t in (("eps3", eps3), ("latents", latents), ("coef", coef)):
-        _f32(t, n)
-    if coef.numel() != 8 or eps3.numel() != 3 * latents.numel():
-        raise ValueError("cfg_ddim_var_step: eps3 must hold 3 latents, coef 8 floats")
-    if latents3 is not None and (latents3.dtype != torch.float32 or latents3.numel() != 3 * latents.numel()):
-        raise ValueError("cfg_ddim_var_step: latents3 must be fp32 and hold 3 latents")
     if noise is not None and (noise.dtype != torch.float32 or noise.numel() != latents.numel() or not noise.is_contiguous()):
         raise ValueError("cfg_ddim_var_step: noise must be contiguous fp32 of the latents' size")
-    N = latents.shape[0]
-    check(lib.sg_cfg_ddim_var_step_f32(eps3.data_ptr(), latents.data_ptr(), _p(latents3), _p(noise), coef.data_ptr(), N,
-                                       latents[0].numel(), _stream()), "sg_cfg_ddim_var_step_f32")
-    return latents
+    return _cfg_step("cfg_ddim_var_step", eps3, latents, latents3, coef, 8, noise)
 
 
 def cfg_plms_step(eps3: torch.Tensor, latents: torch.Tensor, latents3: Optional[torch.Tensor], history: torch.Tensor,
                   kept: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
-    """Guidance combine + PNDM/PLMS update (sg_cfg_plms_step_f32); history fp32 [4, *latents.shape], kept like latents."""
-    for n, t in (("eps3", eps3), ("latents", latents), ("history", history), ("kept", kept), ("coef", coef)):
-        _f32(t, n)
-    if history.numel() != 4 * latents.numel() or kept.numel() != latents.numel() or coef.numel() != 15:
-        raise ValueError("cfg_plms_step: history must hold 4 latents, kept 1, coef 15 floats")
-    N = latents.shape[0]
-    check(lib.sg_cfg_plms_step_f32(eps3.data_ptr(), latents.data_ptr(), _p(latents3), history.data_ptr(), kept.data_ptr(),
-                                   coef.data_ptr(), N, latents[0].numel(), _stream()), "sg_cfg_plms_step_f32")
-    return latents
+    """Guidance combine + PNDM/PLMS update (sg_cfg_plms_step_f32); history fp32 [4, *latents.shape], kept like latents, coef = the 2
+    guidance scales + PNDMSchedule.step_row (15 floats)."""
+    _f32(history, "history"), _f32(kept, "kept")
+    if history.numel() != 4 * latents.numel() or kept.numel() != latents.numel():
+        raise ValueError("cfg_plms_step: history must hold 4 latents, kept 1")
+    return _cfg_step("cfg_plms_step", eps3, latents, latents3, coef, 15, history, kept)
 
 
 def cfg_dpm_step(eps3: torch.Tensor, latents: torch.Tensor, latents3: Optional[torch.Tensor], history: torch.Tensor,
                  coef: torch.Tensor) -> torch.Tensor:
     """Guidance combine + DPM-Solver multistep update (sg_cfg_dpm_step_f32); history fp32 [3, *latents.shape] (converted model
     outputs), coef = the 2 guidance scales + DPMSolverMultistepSchedule.step_row (12 floats)."""
-    for n, t in (("eps3", eps3), ("latents", latents), ("history", history), ("coef", coef)):
-        _f32(t, n)
-    if history.numel() != 3 * latents.numel() or coef.numel() != 12 or eps3.numel() != 3 * latents.numel():
-        raise ValueError("cfg_dpm_step: eps3 and history must hold 3 latents each, coef 12 floats")
-    if latents3 is not None and (latents3.dtype != torch.float32 or latents3.numel() != 3 * latents.numel()):
-        raise ValueError("cfg_dpm_step: latents3 must be fp32 and hold 3 latents")
-    N = latents.shape[0]
-    check(lib.sg_cfg_dpm_step_f32(eps3.data_ptr(), latents.data_ptr(), _p(latents3), history.data_ptr(), coef.data_ptr(), N,
-                                  latents[0].numel(), _stream()), "sg_cfg_dpm_step_f32")
-    return latents
+    _f32(history, "history")
+    if history.numel() != 3 * latents.numel():
+        raise ValueError("cfg_dpm_step: history must hold 3 latents")
+    return _cfg_step("cfg_dpm_step", eps3, latents, latents3, coef, 12, history)
 
 
 def copy_rows(dst: torch.Tensor, src: torch.Tensor) -> torch.Tensor:

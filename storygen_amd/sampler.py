@@ -3,8 +3,9 @@
 One `step()` is one iteration of /root/reference/model/pipeline.py:412-461 with classifier-free guidance: the
 reference passes that harvest the 16 diffusion features of every prior frame (:418-438), one main pass (batch 3N:
 latents x3 with [uncond, uncond, text]) whose attn3 cross-attends to them (:440-453), the 3-way guidance combine
-(:457-458) and the scheduler's update (:461): DDIM, PNDM/PLMS or multistep DPM-Solver, each one elementwise kernel driven by a
-row of host-computed scalars per step (storygen_amd/scheduler.py), so the step graph is the same for all three.
+(:457-458) and the scheduler's update (:461).  The sampler holds the schedule's UpdateRule (storygen_amd/scheduler.py: DDIM, DDIM
+with eta / clip_sample, PNDM/PLMS, multistep DPM-Solver): one elementwise kernel driven by a row of host-computed scalars per step,
+plus the buffers it keeps between steps, so the step graph has the same shape for all of them.
 
 MI355X-first structure
   * The R reference passes are ONE batched UNet call.  As written, pass i runs the batch [zero_i, img_i, img_i] with
@@ -142,15 +143,11 @@ class StoryGenSampler:
         self.latents = torch.zeros(lat_shape, **f32)
         self.latents3 = torch.zeros((self.B,) + lat_shape[1:], **f32)
         self.noise = torch.zeros(lat_shape, **f32)
-        if self.schedule.kind == "plms":          # PNDM: ring of the last 4 guided epsilons + the sample kept by the first call
-            self.eps_history = torch.zeros((4,) + lat_shape, **f32)
-            self.kept_sample = torch.zeros(lat_shape, **f32)
-        elif self.schedule.kind == "dpm":         # DPM-Solver: ring of the last 3 converted model outputs (fp32: x0 = (x - sigma e) / alpha)
-            self.model_outputs = torch.zeros((3,) + lat_shape, **f32)
-        # DDIM with eta > 0 or clip_sample (prepare(eta=...)): the update kernel is sg_cfg_ddim_var_step_f32, a table row carries its
-        # six scalars, and the variance noise of step k is staged from `var_noise_all` [steps, N, 4, h, w] (filled by prepare()) into
-        # `var_noise` [G, N, 4, h, w] — the buffer the captured graphs read — beside the upload of the step's parameter row(s)
-        self.var = False
+        # the update rule (chosen by prepare(eta=...)) and the buffers its kernel keeps between steps.  A rule that needs noise (DDIM
+        # with eta > 0 or clip_sample): the variance noise of step k is staged from `var_noise_all` [steps, N, 4, h, w] (filled by
+        # prepare()) into `var_noise` [G, N, 4, h, w] — the buffer the captured graphs read — beside the upload of the step's row(s)
+        self.rule = None
+        self.rule_state: Dict[str, torch.Tensor] = {}
         self.eta = 0.0
         self.var_noise: Optional[torch.Tensor] = None
         self.var_noise_all: Optional[torch.Tensor] = None
@@ -161,6 +158,10 @@ class StoryGenSampler:
     @property
     def engine(self) -> UNetEngine:   # the main-pass engine
         return self.main
+
+    @property
+    def var(self) -> bool:            # the eta / clip_sample rule is in use
+        return self.rule is not None and self.rule.needs_noise
 
     # ------------------------------------------------------------------------------------------------ layout
     def _plan(self, stage: str, share_zero: bool):
@@ -228,7 +229,7 @@ class StoryGenSampler:
             self.ref, self.ctx_sets, self.kv_sets, self.plans = None, [], [], []
             self.side_main = torch.cuda.Stream(device=self.dev) if self.use_graph else None
             self.side_ref = None
-            self.n_par = self.B + 2 + self._row_len()
+            self.n_par = self.B + 2 + self.rule.row_len
             self.params = torch.zeros(1, self.n_par, dtype=torch.float32, device=self.dev)
             self.lat_trace, self.group_direct = None, False
             self.layout, self.graph, self.graphs, self.g_ref, self.g_main, self.tails = key, None, [], [], [], {}
@@ -295,7 +296,7 @@ class StoryGenSampler:
         self.ref_noise = torch.zeros((self.U,) + tuple(self.latents.shape[1:]), **f32)
         # per-step parameters, one row per step of a group (G rows; only the group schedule reads rows > 0):
         # [U] ref timesteps | [B] main timestep | [U,2] add_noise coefs | guidance + update-rule coefs
-        self.n_par = 3 * self.U + self.B + 2 + self._row_len()
+        self.n_par = 3 * self.U + self.B + 2 + self.rule.row_len
         self.params = torch.zeros(G if self.group else 1, self.n_par, **f32)
         self.lat_trace = torch.zeros((G,) + tuple(self.latents.shape), **f32) if self.group else None
         self.layout, self.graph, self.graphs, self.tails = key, None, [], {}
@@ -307,10 +308,6 @@ class StoryGenSampler:
             if self.stream_priority:
                 self.main_stream = torch.cuda.Stream(device=self.dev, priority=-1)
             self.ev_ref = [torch.cuda.Event(), torch.cuda.Event()]      # "reference pass of a group of this parity is done"
-
-    def _row_len(self) -> int:
-        """Update-rule scalars per table row: the schedule's own, or (sa, sb, sap, dir, std, clip) on the eta / clip_sample path."""
-        return 6 if self.var else self.schedule.row_len
 
     def _par_views(self, row: int = 0):
         """(reference timesteps [U], main timesteps [B], add_noise coefficients [U, 2], guidance + update-rule scalars) of parameter
@@ -334,12 +331,11 @@ class StoryGenSampler:
             raise ValueError("only the classifier-free-guidance path of the reference loop works (SURVEY F6g)")
         if not eta >= 0.0:
             raise ValueError(f"eta = {eta!r}: diffusers' DDIM eta lies in [0, 1]")
-        ddim = self.schedule.kind == "ddim"
-        eta = float(eta) if ddim else 0.0
-        var = ddim and (eta > 0.0 or bool(getattr(self.schedule, "clip_sample", False)))
-        if var != self.var:                       # another update kernel and row length: parameter block and graphs are rebuilt
-            self.var, self.layout = var, None
-        self.eta = eta
+        rule = self.schedule.update_rule(float(eta))
+        if self.rule is None or rule.key != self.rule.key:      # another update kernel and row length: its state is allocated, the
+            self.rule_state = rule.state(tuple(self.latents.shape), self.dev)     # parameter block and the graphs are rebuilt
+            self.layout = None
+        self.rule, self.eta = rule, rule.eta
         dev, N, R = self.dev, self.N, self.R
         pu = inputs["prev_uncond"]
         share_zero = (self.dedup and stage == "multi-image-condition"
@@ -348,7 +344,7 @@ class StoryGenSampler:
         # ---- the per-step table: host arithmetic only
         ts = self.schedule.timesteps(num_inference_steps)
         rows, row0 = step_table(self.schedule, ts, num_inference_steps, self.units[:self.U0], R, stage, self.B, self.G,
-                                self.ahead and not self.no_ctx, image_guidance_scale, guidance_scale, eta=eta if self.var else None)
+                                self.ahead and not self.no_ctx, image_guidance_scale, guidance_scale, eta=self.eta)
         if self.group and len(rows) % self.G:
             raise ValueError(f"ref_ahead = {self.G} runs the loop in groups of {self.G} UNet evaluations: {len(rows)} evaluations "
                              f"({num_inference_steps} inference steps) is not a multiple")
@@ -467,14 +463,8 @@ class StoryGenSampler:
         main.x_in.copy_(self.latents3)                                                    # :448-453
         main.t_in.copy_(t_main)
         eps3 = main.forward(consume=not self.no_ctx, text_cache=True, side=self.side_main)
-        if self.var:                                                                      # :457-461, DDIM with eta / clip_sample
-            ops.cfg_ddim_var_step(eps3, self.latents, self.latents3, self.var_noise[row], cd)
-        elif self.schedule.kind == "plms":
-            ops.cfg_plms_step(eps3, self.latents, self.latents3, self.eps_history, self.kept_sample, cd)
-        elif self.schedule.kind == "dpm":
-            ops.cfg_dpm_step(eps3, self.latents, self.latents3, self.model_outputs, cd)
-        else:
-            ops.cfg_ddim_step(eps3, self.latents, self.latents3, cd)
+        noise = self.var_noise[row] if self.rule.needs_noise else None
+        self.rule.launch(ops, eps3, self.latents, self.latents3, self.rule_state, noise, cd)      # :457-461
 
     def _group_body(self, parity: int, side: Optional["torch.cuda.Stream"], with_ref: bool = True):
         """Group schedule: the G main passes of a group of this parity (context sets parity*G ..) and, beside them, the batched
@@ -724,9 +714,8 @@ def step_table(schedule: DDIMSchedule, ts, num_inference_steps: int, units0, R: 
     """The scalars every denoising step needs, as rows of the pinned table the sampler uploads from (pure host logic).
 
     Row k = [U reference timesteps | B main timesteps | U x 2 add_noise coefficients | 2 guidance scales + the update
-    rule's scalars (schedule.step_row: 4 for DDIM, 13 for PNDM/PLMS, 10 for DPM-Solver)], U = G * len(units0).  units0 = the (kind, frame, sample) reference samples of ONE step.
-    eta (a number, DDIM only): the eta / clip_sample path — the rule's scalars are the 6 of sg_cfg_ddim_var_step_f32,
-    (*schedule.var_step_coef(t, n, eta), clip_sample); None (default) = the schedule's own row.
+    rule's scalars (schedule.update_rule(eta).row: 4 for DDIM, 6 with eta / clip_sample, 13 for PNDM/PLMS, 10 for DPM-Solver)],
+    U = G * len(units0).  units0 = the (kind, frame, sample) reference samples of ONE step.  eta None (default) = the schedule's own step_row.
     Which reference scalars row k carries depends on the schedule of the passes:
       no overlap          : those of step k itself (reference pass, then main pass);
       overlap, G = 1      : those of step k+1 (graph k runs main pass k beside reference pass k+1);
@@ -735,12 +724,7 @@ def step_table(schedule: DDIMSchedule, ts, num_inference_steps: int, units0, R: 
     Steps past the end repeat the last timestep (their features are never consumed).  Also returns row0: the reference
     scalars of the very first pass / group (the one nothing overlaps with), main part zero."""
     T = len(ts)
-    row_len = schedule.row_len if eta is None else 6
-
-    def rule(k):
-        if eta is None:
-            return schedule.step_row(k, ts, num_inference_steps)
-        return [*schedule.var_step_coef(int(ts[k]), num_inference_steps, eta), float(schedule.clip_sample)]
+    rule = schedule.update_rule(eta)
 
     def ref_part(t):
         ref_t = int(t) // 10                                                              # pipeline.py:414-415
@@ -765,10 +749,10 @@ def step_table(schedule: DDIMSchedule, ts, num_inference_steps: int, units0, R: 
         else:
             tt, cc = ref_part(ts[min(k + 1, T - 1)] if overlap else t)
         row = tt + [float(t)] * B + cc
-        row += [image_guidance_scale, guidance_scale, *rule(k)]
+        row += [image_guidance_scale, guidance_scale, *rule.row(k, ts, num_inference_steps)]
         rows.append(row)
     tt, cc = group_ref(0) if G > 1 else ref_part(ts[0])
-    return rows, tt + [float(ts[0])] * B + cc + [0.0] * (2 + row_len)
+    return rows, tt + [float(ts[0])] * B + cc + [0.0] * (2 + rule.row_len)
 
 
 def gather_latents(latents: torch.Tensor) -> torch.Tensor:

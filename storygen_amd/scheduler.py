@@ -8,15 +8,81 @@ names (`_class_name: PNDMScheduler`, skip_prk_steps=true) — the PLMS linear-mu
 DPMSolverMultistepSchedule: DPM-Solver / DPM-Solver++ multistep (diffusers 0.13.1 `DPMSolverMultistepScheduler`, which
 model/pipeline.py:7-16 also accepts), restated from the published formulas (Lu et al. 2022, "DPM-Solver" and "DPM-Solver++").
 Reference call sites: model/pipeline.py:7-16,47-75 (accepted scheduler classes), :366-367 (set_timesteps), :420-424
-(add_noise), :461 (step)."""
+(add_noise), :461 (step).
+
+A schedule is the numbers; what the sampler does with them each step is its UpdateRule (`schedule.update_rule(eta)`): the one `ops`
+entry point it launches, the scalars of a table row, and the fp32 buffers that kernel keeps between steps."""
 from __future__ import annotations
 
 import json
 import math
 import os
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 import torch
+
+
+class UpdateRule:
+    """All the sampling loop knows about a scheduler's `step`.  This one is plain DDIM (sg_cfg_ddim_step_f32): no state, the row is
+    the schedule's own `step_row`; the others override what differs."""
+    key = "ddim"                 # hashable: rules with equal keys launch the same kernel on rows of the same length
+    needs_noise = False          # the kernel adds std * noise (the sampler stages the step's variance noise for it)
+    eta = 0.0
+
+    def __init__(self, schedule: "DDIMSchedule"):
+        self.schedule = schedule
+        self.row_len = schedule.row_len          # scalars of a table row after the two guidance scales
+
+    def row(self, k: int, ts: List[int], n: int) -> List[float]:
+        return self.schedule.step_row(k, ts, n)
+
+    def state(self, shape, device) -> Dict[str, torch.Tensor]:
+        """The buffers the kernel keeps between the steps of a loop over latents of `shape`."""
+        return {}
+
+    def launch(self, ops, eps3, latents, latents3, state, noise, coef):
+        ops.cfg_ddim_step(eps3, latents, latents3, coef)
+
+
+class DDIMVarRule(UpdateRule):
+    """DDIM with eta > 0 and / or clip_sample (sg_cfg_ddim_var_step_f32): row = (sa, sb, sap, dir, std, clip)."""
+    key = "ddim-var"
+    needs_noise = True
+
+    def __init__(self, schedule: "DDIMSchedule", eta: float):
+        self.schedule, self.eta, self.row_len = schedule, float(eta), 6
+
+    def row(self, k, ts, n):
+        return [*self.schedule.var_step_coef(int(ts[k]), n, self.eta), float(self.schedule.clip_sample)]
+
+    def launch(self, ops, eps3, latents, latents3, state, noise, coef):
+        ops.cfg_ddim_var_step(eps3, latents, latents3, noise, coef)
+
+
+def _zeros(shape, device) -> torch.Tensor:
+    return torch.zeros(tuple(shape), dtype=torch.float32, device=device)
+
+
+class PLMSRule(UpdateRule):
+    """PNDM / PLMS (sg_cfg_plms_step_f32): a ring of the last 4 guided epsilons and the sample kept by the first call."""
+    key = "plms"
+
+    def state(self, shape, device):
+        return {"history": _zeros((4, *shape), device), "kept": _zeros(shape, device)}
+
+    def launch(self, ops, eps3, latents, latents3, state, noise, coef):
+        ops.cfg_plms_step(eps3, latents, latents3, state["history"], state["kept"], coef)
+
+
+class DPMRule(UpdateRule):
+    """Multistep DPM-Solver (sg_cfg_dpm_step_f32): a ring of the last 3 converted model outputs (fp32: x0 = (x - sigma e) / alpha)."""
+    key = "dpm"
+
+    def state(self, shape, device):
+        return {"history": _zeros((3, *shape), device)}
+
+    def launch(self, ops, eps3, latents, latents3, state, noise, coef):
+        ops.cfg_dpm_step(eps3, latents, latents3, state["history"], coef)
 
 
 # keys of a compatible scheduler's config that do not change the DDIM / PLMS arithmetic (diffusers ignores them the same way
@@ -25,8 +91,7 @@ _IGNORED_KEYS = ("_class_name", "_diffusers_version", "_name_or_path", "_use_def
 
 
 class DDIMSchedule:
-    kind = "ddim"          # which update kernel the sampler launches (ddim: sg_cfg_ddim_step_f32, plms: sg_cfg_plms_step_f32,
-    #                        dpm: sg_cfg_dpm_step_f32)
+    kind = "ddim"          # the family of the update rule (update_rule() hands out the rule itself)
     row_len = 4            # floats step_row() contributes to a row of the sampler's per-step table
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
@@ -85,6 +150,13 @@ class DDIMSchedule:
         """Hashable identity of the schedule (cache key of the pipeline's sampler)."""
         c = self._config
         return (type(self).__name__,) + tuple((k, tuple(v) if isinstance(v, list) else v) for k, v in sorted(c.items()))
+
+    def update_rule(self, eta: Optional[float] = 0.0) -> UpdateRule:
+        """What the loop launches each step at diffusers' `eta` (pipeline.py:208-221,461 hands it to DDIM only: PNDM and DPM-Solver
+        ignore it).  eta = None: the plain rule whatever clip_sample says (the schedule's own step_row)."""
+        if eta is None or (eta == 0 and not self.clip_sample):
+            return UpdateRule(self)
+        return DDIMVarRule(self, eta)
 
     def step_row(self, k: int, ts: List[int], n: int) -> List[float]:
         """The scalars the update kernel needs at loop index k (timesteps `ts` = self.timesteps(n))."""
@@ -163,6 +235,9 @@ class PNDMSchedule(DDIMSchedule):
         self._config.pop("set_alpha_to_one", None)
         self._config.pop("clip_sample", None)            # not a PNDMScheduler key
         self._config["set_alpha_to_one"] = kw.get("set_alpha_to_one", False)
+
+    def update_rule(self, eta: Optional[float] = 0.0) -> UpdateRule:
+        return PLMSRule(self)
 
     def timesteps(self, n: int) -> List[int]:
         ratio = self.num_train_timesteps // n
@@ -267,6 +342,9 @@ class DPMSolverMultistepSchedule(DDIMSchedule):
         cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
         cfg.update(kwargs)
         return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
+
+    def update_rule(self, eta: Optional[float] = 0.0) -> UpdateRule:
+        return DPMRule(self)
 
     def timesteps(self, n: int) -> List[int]:
         import numpy as np          # numpy's linspace + round-half-to-even, exactly as `set_timesteps` computes them

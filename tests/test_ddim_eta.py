@@ -122,8 +122,8 @@ def test_pipeline_draws_variance_noise_in_reference_order_generator_list(monkeyp
 
 
 def test_pipeline_eta_zero_and_pndm_draw_nothing(monkeypatch):
-    """eta = 0 consumes the generator exactly as before the eta path existed (prepare_latents' one draw) and calls prepare() as it
-    always did; PNDM ignores eta (prepare_extra_step_kwargs forwards it only to schedulers whose step takes it)."""
+    """eta = 0 consumes the generator exactly as before the eta path existed (prepare_latents' one draw) and hands prepare() eta = 0
+    and no noise; PNDM and DPM-Solver ignore eta (prepare_extra_step_kwargs forwards it only to schedulers whose step takes it)."""
     from storygen_amd.scheduler import DDIMSchedule, DPMSolverMultistepSchedule, PNDMSchedule
     after_latents = torch.Generator().manual_seed(99)
     torch.randn((1, 4, 8, 8), generator=after_latents)
@@ -133,7 +133,7 @@ def test_pipeline_eta_zero_and_pndm_draw_nothing(monkeypatch):
         g = torch.Generator().manual_seed(99)
         cpu_call(pipe, 1, steps, eta=eta, generator=g)
         (kw,) = RecordingSampler.made[0].prepared
-        assert kw == {"steps": steps}, (type(sched).__name__, kw)
+        assert kw == {"steps": steps, "eta": 0.0, "variance_noise": None}, (type(sched).__name__, kw)
         assert torch.equal(g.get_state(), after_latents.get_state()), type(sched).__name__
 
 

@@ -118,7 +118,7 @@ def test_order1_dpm_solver_pp_on_ddim_timesteps_vs_reference_golden_64x64(gpu, s
     print(f"order-1 DPM-Solver++ on DDIM timesteps, ref_ahead={G}: steps 0/9/24/49", [f"{errs[i]:.2e}" for i in (0, 9, 24, 49)],
           f"max {max(errs):.2e}")
     assert len(errs) == 50 and max(errs) <= TOL_LATENT, errs
-    assert torch.isfinite(smp.model_outputs).all() and smp.model_outputs.abs().sum() > 0      # the ring was written
+    assert torch.isfinite(smp.rule_state["history"]).all() and smp.rule_state["history"].abs().sum() > 0      # the ring was written
     smp.check_guards()
 
 
