@@ -10,7 +10,9 @@ bumped, so the drop-in UNet's weight-staleness tag sees the change); gradients c
 `UNetTrainer.train_step*` returns (`set_grads`).  A whole step is a handful of launches per tensor and no host read: the global-norm
 clipping coefficient is computed on the device.  bitsandbytes is CUDA-only, so AdamW8bit restates its published block-wise algorithm
 (2048-element blocks, dynamic-tree code books, per-block absmax); tensors below `min_8bit_size` elements keep fp32 states, as there.
-No CPU path: importing this module loads libstorygen_hip.so."""
+Bias corrections use a PER-PARAMETER step number (state[i]["step"], as torch.optim.AdamW and bitsandbytes keep it): it counts the updates
+of that tensor, so a parameter whose first gradient arrives late starts at 1; `step_count` counts `step()` calls (what the scheduler and the
+checkpoints see).  No CPU path: importing this module loads libstorygen_hip.so."""
 from __future__ import annotations
 
 import ctypes as C
@@ -75,6 +77,7 @@ class AdamW:
         self._total = torch.zeros(1, dtype=torch.float32, device=self.dev)                   # ... and their sum, read by the step kernels
         self._scratch = torch.empty(lib.sg_sumsq_scratch_floats(), dtype=torch.float32, device=self.dev)
         self._clip: Optional[float] = None
+        self._clip_scale = 1.0
         if self.eight_bit:
             self._code1, self._code2 = create_dynamic_map(True).to(self.dev), create_dynamic_map(False).to(self.dev)
             self._zero1 = int((self._code1 == 0).nonzero()[0])
@@ -96,21 +99,26 @@ class AdamW:
             raise TypeError(f"gradient of {self.names[i]} must be an fp32 CUDA tensor of {self.params[i].numel()} elements")
         return g if g.is_contiguous() else g.contiguous()
 
-    def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
+    def clip_grad_norm_(self, max_norm: float, grad_scale: float = 1.0) -> torch.Tensor:
         """torch.nn.utils.clip_grad_norm_ over every parameter that has a gradient: returns the total norm (a device scalar — reading
-        it is the caller's choice) and arms the clipping of the next `step()`, which scales the gradients on the fly."""
+        it is the caller's choice) and arms the clipping of the next `step()`, which scales the gradients on the fly.  When the
+        gradients still carry a loss scale, pass its inverse as `grad_scale` (the one `step()` will use): the norm returned and
+        clipped on is that of the UNSCALED gradients, grad_scale * |g|, as clipping after GradScaler.unscale_ gives."""
+        if not float(grad_scale) > 0.0:
+            raise ValueError(f"clip_grad_norm_: grad_scale must be positive, got {grad_scale}")
         self._sumsq.zero_()
         for i in range(len(self.params)):
             g = self._grad(i)
             if g is not None:
                 check(lib.sg_sumsq_f32(g.data_ptr(), g.numel(), self._sumsq[i:].data_ptr(), self._scratch.data_ptr(), _stream()), "sg_sumsq_f32")
         torch.sum(self._sumsq, dim=0, keepdim=True, out=self._total)
-        self._clip = float(max_norm)
-        return self._total.sqrt()[0]
+        self._clip, self._clip_scale = float(max_norm), float(grad_scale)
+        norm = self._total.sqrt()[0]
+        return norm if self._clip_scale == 1.0 else norm * self._clip_scale
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         self._grads = None
-        self._clip = None
+        self._clip, self._clip_scale = None, 1.0
         for p in self.params:
             if getattr(p, "grad", None) is not None:
                 p.grad = None
@@ -123,20 +131,26 @@ class AdamW:
             n = p.numel()
             if self.eight_bit and n >= self.min_8bit_size:
                 nb = lib.sg_adamw8bit_blocks(n)
-                st = dict(bits=8, code1=torch.full((n,), self._zero1, dtype=torch.uint8, device=self.dev),
+                st = dict(bits=8, step=0, code1=torch.full((n,), self._zero1, dtype=torch.uint8, device=self.dev),
                           code2=torch.full((n,), self._zero2, dtype=torch.uint8, device=self.dev),
                           absmax1=torch.zeros(nb, dtype=torch.float32, device=self.dev),
                           absmax2=torch.zeros(nb, dtype=torch.float32, device=self.dev))
             else:
-                st = dict(bits=32, exp_avg=torch.zeros(n, dtype=torch.float32, device=self.dev),
+                st = dict(bits=32, step=0, exp_avg=torch.zeros(n, dtype=torch.float32, device=self.dev),
                           exp_avg_sq=torch.zeros(n, dtype=torch.float32, device=self.dev))
             self.state[i] = st
         return st
 
     @torch.no_grad()
-    def step(self, grad_scale: float = 1.0) -> None:
+    def step(self, grad_scale: Optional[float] = None) -> None:
         """One update of every parameter that has a gradient.  grad_scale multiplies the gradients first (1 / loss scale when the
-        caller scaled the loss itself; UNetTrainer's gradients are already unscaled)."""
+        caller scaled the loss itself; UNetTrainer's gradients are already unscaled); default: the scale `clip_grad_norm_` was
+        given, else 1.  A parameter without a gradient keeps its states and its step number."""
+        if grad_scale is None:
+            grad_scale = self._clip_scale if self._clip is not None else 1.0
+        elif self._clip is not None and float(grad_scale) != self._clip_scale:
+            raise ValueError(f"step(grad_scale={grad_scale}) after clip_grad_norm_(..., grad_scale={self._clip_scale}): the norm that was "
+                             "returned is not the one the clip would use")
         self.step_count += 1
         g0 = self.param_groups[0]
         for i, p in enumerate(self.params):
@@ -144,10 +158,11 @@ class AdamW:
             if g is None:
                 continue
             st = self._state(i)
+            st["step"] += 1
             d = AdamWDesc()
             d.param, d.grad, d.n = p.data_ptr(), g.data_ptr(), p.numel()
             d.lr, (d.beta1, d.beta2), d.eps, d.weight_decay = g0["lr"], g0["betas"], g0["eps"], g0["weight_decay"]
-            d.step, d.grad_scale = self.step_count, float(grad_scale)
+            d.step, d.grad_scale = st["step"], float(grad_scale)
             if self._clip is not None:
                 d.sumsq, d.n_sumsq, d.max_norm = self._total.data_ptr(), 1, self._clip
             if st["bits"] == 8:
@@ -159,7 +174,7 @@ class AdamW:
                 d.exp_avg, d.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
                 check(lib.sg_adamw_f32(C.byref(d), _stream()), "sg_adamw_f32")
             torch.autograd.graph.increment_version(p)          # the kernel wrote p behind autograd's back
-        self._clip = None
+        self._clip, self._clip_scale = None, 1.0
 
     # ------------------------------------------------------------------------------------------------ (de)serialisation
     def state_dict(self) -> dict:
@@ -168,6 +183,7 @@ class AdamW:
                                                    for i, st in self.state.items()})
 
     def load_state_dict(self, sd: dict) -> None:
+        """A state dict written before the per-parameter step numbers existed loads with `step_count` for every tensor."""
         self.step_count = int(sd["step"])
         self.param_groups[0].update(sd["param_groups"][0])
         index = {n: i for i, n in enumerate(self.names)}
@@ -177,6 +193,7 @@ class AdamW:
             want = self._state(i)
             if want["bits"] != st["bits"]:
                 raise ValueError(f"optimizer state of {name} is {st['bits']}-bit, this optimizer keeps it in {want['bits']} bits")
+            want["step"] = int(st.get("step", self.step_count))
             for k, v in st.items():
                 if torch.is_tensor(v):
                     want[k].copy_(v)
