@@ -469,6 +469,29 @@ int sg_gaussian_sample_f32(const float* mean, const float* logvar, const float* 
                            sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Front of the CLIP image tower (CLIP-I / CLIP-T scoring of generated frames with a ViT-B/32-class model).  The tower's
+ * GEMMs, LayerNorms, attention and activation are the entry points above; these are the pieces before the first layer.
+ *
+ * sg_clip_resize_geometry: the `clip` package's preprocessing geometry (torchvision Resize(S, BICUBIC) then CenterCrop(S)) for
+ *   an H x W image: the shorter side becomes S, the longer int(S * long / short); the crop offset per axis is
+ *   int(round((size - S) / 2.0)) with halves rounded to the even integer.  geom receives {resized H, resized W, top, left}.
+ * sg_clip_patchify_f16: x fp32 NCHW [B, 3, H, W] -> fp16 rows out[B * P, 3 * ps * ps], P = (S / ps)^2 patches in row-major
+ *   order, columns in (c, dy, dx) order — the A operand of a GEMM against patch_embedding.weight.view(C, 3 * ps * ps).  Each
+ *   value is (in_scale * r + in_shift - mean[c]) / std[c], r the antialiased bicubic resample (Keys kernel a = -0.5, half-pixel
+ *   centres, support 2 * max(in / out, 1) input pixels per axis, window truncated at the edges, weights normalised to sum 1:
+ *   torch.nn.functional.interpolate(mode="bicubic", antialias=True, align_corners=False)) of the image at the pixel of the
+ *   centre crop, in fp32.  mean and std are HOST arrays of 3 floats.  Returns SG_EINVAL without launching when S % ps != 0,
+ *   3 * ps * ps is not a multiple of 8, a size is not positive, a pointer is null or a std is zero.
+ * sg_clip_embed_patches_f32: CLIPVisionEmbeddings' concat and position add on the fp32 residual stream: out[b * T, :] =
+ *   cls + pos[0], out[b * T + t, :] = patches[b * (T - 1) + t - 1, :] + pos[t] for 1 <= t < T.
+ */
+int sg_clip_resize_geometry(int32_t H, int32_t W, int32_t S, int32_t* geom);
+int sg_clip_patchify_f16(const float* x, int32_t B, int32_t H, int32_t W, float in_scale, float in_shift, const float* mean,
+                         const float* std, int32_t S, int32_t ps, sg_half* out, int64_t ldo, sg_stream_t stream);
+int sg_clip_embed_patches_f32(const float* patches, int64_t ldp, const float* cls, const float* pos, float* out, int64_t ldo,
+                              int32_t B, int32_t T, int32_t C, sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimizer step of the training loop: /root/reference/train_StorySalon_stage2.py:186-205 builds torch.optim.AdamW
  * or bitsandbytes' AdamW8bit over the trainable (attn3) parameters, :328-333 clips the global gradient norm and steps.
  *

@@ -210,6 +210,11 @@ SIGNATURES = {
     "sg_embed_tokens_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_void_p]),
     "sg_gaussian_sample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p]),
+    "sg_clip_resize_geometry": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sg_clip_patchify_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sg_clip_embed_patches_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_void_p]),
     "sg_sumsq_scratch_floats": (C.c_size_t, []),
     "sg_sumsq_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sg_adamw_f32": (C.c_int, [C.POINTER(AdamWDesc), C.c_void_p]),

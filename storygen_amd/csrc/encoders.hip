@@ -6,6 +6,9 @@
 //   act_rows_kernel       quick_gelu / gelu between CLIP's fc1 and fc2
 //   embed_tokens_kernel   token + position embedding gather into the fp32 residual stream
 //   gaussian_sample_kernel  DiagonalGaussianDistribution.sample() * scaling factor
+// and the front of the CLIP image tower (CLIP-I / CLIP-T scoring of generated frames):
+//   clip_patchify_kernel       antialiased bicubic resize + centre crop + normalise + patch gather, float image -> fp16 GEMM rows
+//   clip_embed_patches_kernel  class token + patch rows + position embedding into the fp32 residual stream
 #include "common.h"
 
 namespace {
@@ -137,6 +140,94 @@ __global__ __launch_bounds__(256) void gaussian_sample_kernel(const float* mean,
     }
 }
 
+// ---- CLIP image tower front end (the `clip` package's preprocessing = torchvision Resize(S, BICUBIC) + CenterCrop(S) + Normalize, then
+// the patch gather of CLIPVisionEmbeddings' stride-ps convolution), one launch.
+// Keys cubic, a = -0.5
+__device__ __forceinline__ float keys_cubic(float x) {
+    x = fabsf(x);
+    if (x < 1.0f) return ((1.5f * x - 2.5f) * x) * x + 1.0f;
+    if (x < 2.0f) return (((x - 5.0f) * x + 8.0f) * x - 4.0f) * -0.5f;
+    return 0.0f;
+}
+
+// Antialiased window of output index i along an axis of `in` input pixels (scale = in / out, half-pixel centres): taps [lo, lo + n) lie
+// inside the image by construction (the window is truncated at the edges and the weights renormalised by their sum).
+__device__ __forceinline__ void aa_window(int i, int in, float scale, int& lo, int& n, float& center, float& inv) {
+    const float support = scale >= 1.0f ? 2.0f * scale : 2.0f;
+    center = scale * ((float)i + 0.5f);
+    inv = scale >= 1.0f ? 1.0f / scale : 1.0f;
+    lo = max((int)(center - support + 0.5f), 0);
+    n = max(min((int)(center + support + 0.5f), in) - lo, 0);
+}
+
+struct PatchifyArgs {
+    int B, H, W, S, ps, RH, RW, top, left;      // input size, crop size, patch size, resized size, crop offset in the resized image
+    float sy, sx;                               // H / RH, W / RW
+    float in_scale, in_shift, mean[3], std[3];
+};
+
+// One resampled, normalised value: image b, output column col = (c * ps + dy) * ps + dx of the patch at (py, px).
+__device__ __forceinline__ float patchify_value(const float* x, const PatchifyArgs& a, int b, int py, int px, int col) {
+    const int c = col / (a.ps * a.ps), rem = col - c * a.ps * a.ps;
+    const int dy = rem / a.ps, dx = rem - dy * a.ps;
+    int ylo, ny, xlo, nx;
+    float cy, iy, cx, ix;
+    aa_window(a.top + py * a.ps + dy, a.H, a.sy, ylo, ny, cy, iy);
+    aa_window(a.left + px * a.ps + dx, a.W, a.sx, xlo, nx, cx, ix);
+    float ty = 0.f, tx = 0.f;
+    for (int j = 0; j < ny; ++j) ty += keys_cubic(((float)(ylo + j) - cy + 0.5f) * iy);
+    for (int k = 0; k < nx; ++k) tx += keys_cubic(((float)(xlo + k) - cx + 0.5f) * ix);
+    const float* src = x + ((long)b * 3 + c) * a.H * a.W;
+    float acc = 0.f;
+    for (int j = 0; j < ny; ++j) {
+        const float* r = src + (long)(ylo + j) * a.W + xlo;
+        float s = 0.f;
+        for (int k = 0; k < nx; ++k) s += keys_cubic(((float)(xlo + k) - cx + 0.5f) * ix) * r[k];
+        acc += keys_cubic(((float)(ylo + j) - cy + 0.5f) * iy) * s;
+    }
+    const float t = ty * tx;
+    if (t != 0.f) acc /= t;
+    // the input affine commutes with the resampling (the normalised weights sum to one), so it is applied once here
+    const float v = acc * a.in_scale + a.in_shift;
+    const float m = c == 0 ? a.mean[0] : (c == 1 ? a.mean[1] : a.mean[2]);
+    const float sd = c == 0 ? a.std[0] : (c == 1 ? a.std[1] : a.std[2]);
+    return (v - m) / sd;
+}
+
+// One thread per 8 consecutive columns of one output row (one 16-byte store).  Row = b * P + patch (row-major patches), column =
+// (c * ps + dy) * ps + dx: the layout of patch_embedding.weight.view(C, 3 * ps * ps).  The separable weights are evaluated per output
+// value (<= 11 x 11 taps at 512 -> 224): no intermediate image, fp32 throughout.
+__global__ __launch_bounds__(256) void clip_patchify_kernel(const float* x, f16* out, long ldo, PatchifyArgs a) {
+    const int K = 3 * a.ps * a.ps, vpr = K / 8, G = a.S / a.ps, P = G * G;
+    const long total = (long)a.B * P * vpr;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long row = idx / vpr;
+        const int col0 = (int)(idx - row * vpr) * 8;
+        const int b = (int)(row / P), p = (int)(row - (long)b * P);
+        const int py = p / G, px = p - py * G;
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = patchify_value(x, a, b, py, px, col0 + e);
+        store8h(out + row * ldo + col0, o);
+    }
+}
+
+// CLIPVisionEmbeddings: out[b*T + 0, :] = cls + pos[0], out[b*T + t, :] = patches[b*(T-1) + t-1, :] + pos[t]   (fp32)
+__global__ __launch_bounds__(256) void clip_embed_patches_kernel(const float* patches, long ldp, const float* cls, const float* pos, float* out,
+                                                                 long ldo, int rows, int T, int C) {
+    const int vpr = C / 4;
+    const long total = (long)rows * vpr;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long r = idx / vpr;
+        const int c = (int)(idx - r * vpr) * 4;
+        const long b = r / T;
+        const int t = (int)(r - b * T);
+        const float4 a = *reinterpret_cast<const float4*>(t == 0 ? cls + c : patches + (b * (T - 1) + t - 1) * ldp + c);
+        const float4 p = *reinterpret_cast<const float4*>(pos + (long)t * C + c);
+        *reinterpret_cast<float4*>(out + r * ldo + c) = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
+    }
+}
+
 }  // namespace
 
 extern "C" int sg_softmax_rows_f16(const float* s, int64_t lds, sg_half* p, int64_t ldp, int32_t M, int32_t N, float scale,
@@ -197,5 +288,58 @@ extern "C" int sg_gaussian_sample_f32(const float* mean, const float* logvar, co
     const int blocks = (int)(n / 256 + 1 < 4096 ? n / 256 + 1 : 4096);
     hipLaunchKernelGGL(gaussian_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mean, logvar, noise, out, scale, (long)n);
     SG_CHECK_LAUNCH("sg_gaussian_sample_f32");
+    return SG_OK;
+}
+
+// torchvision's Resize(S) (shorter side -> S, longer side -> int(S * long / short)) followed by CenterCrop(S) (offset
+// int(round((size - S) / 2.0)), Python's round: halves go to the even integer).  geom = {resized H, resized W, top, left}.
+extern "C" int sg_clip_resize_geometry(int32_t H, int32_t W, int32_t S, int32_t* geom) {
+    SG_REQUIRE(geom, "sg_clip_resize_geometry: null pointer");
+    SG_REQUIRE(H > 0 && W > 0 && S > 0 && H <= (1 << 15) && W <= (1 << 15) && S <= (1 << 15), "sg_clip_resize_geometry: bad size H=%d W=%d S=%d", H, W, S);
+    const int shortside = W <= H ? W : H, longside = W <= H ? H : W;
+    const int rl = (int)((double)((long)S * longside) / (double)shortside);
+    const int RH = W <= H ? rl : S, RW = W <= H ? S : rl;
+    const int dh = RH - S, dw = RW - S;
+    geom[0] = RH;
+    geom[1] = RW;
+    geom[2] = (dh >> 1) + ((dh & 1) & (dh >> 1));      // k + 1/2 rounds to the even one of k, k + 1
+    geom[3] = (dw >> 1) + ((dw & 1) & (dw >> 1));
+    return SG_OK;
+}
+
+extern "C" int sg_clip_patchify_f16(const float* x, int32_t B, int32_t H, int32_t W, float in_scale, float in_shift, const float* mean,
+                                    const float* std, int32_t S, int32_t ps, sg_half* out, int64_t ldo, sg_stream_t stream) {
+    SG_REQUIRE(x && mean && std && out, "sg_clip_patchify: null pointer");
+    SG_REQUIRE(B > 0 && H > 0 && W > 0 && S > 0 && ps > 0 && H <= (1 << 15) && W <= (1 << 15) && S <= (1 << 15),
+               "sg_clip_patchify: bad size B=%d H=%d W=%d S=%d ps=%d", B, H, W, S, ps);
+    SG_REQUIRE(S % ps == 0, "sg_clip_patchify: the crop size %d is not a multiple of the patch size %d", S, ps);
+    SG_REQUIRE((3 * ps * ps) % 8 == 0, "sg_clip_patchify: 3 * ps * ps (%d) must be a multiple of 8", 3 * ps * ps);
+    SG_REQUIRE(ldo % 8 == 0 && ldo >= 3 * ps * ps && sg_aligned16(out), "sg_clip_patchify: output row stride / alignment");
+    SG_REQUIRE(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "sg_clip_patchify: zero std");
+    int32_t g[4];
+    if (int e = sg_clip_resize_geometry(H, W, S, g)) return e;
+    PatchifyArgs a;
+    a.B = B, a.H = H, a.W = W, a.S = S, a.ps = ps, a.RH = g[0], a.RW = g[1], a.top = g[2], a.left = g[3];
+    a.sy = (float)H / (float)a.RH, a.sx = (float)W / (float)a.RW;
+    a.in_scale = in_scale, a.in_shift = in_shift;
+    for (int c = 0; c < 3; ++c) a.mean[c] = mean[c], a.std[c] = std[c];
+    const long total = (long)B * (S / ps) * (S / ps) * (3 * ps * ps / 8);
+    const int blocks = (int)(total / 256 + 1 < 65536 ? total / 256 + 1 : 65536);
+    hipLaunchKernelGGL(clip_patchify_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<f16*>(out), (long)ldo, a);
+    SG_CHECK_LAUNCH("sg_clip_patchify_f16");
+    return SG_OK;
+}
+
+extern "C" int sg_clip_embed_patches_f32(const float* patches, int64_t ldp, const float* cls, const float* pos, float* out, int64_t ldo,
+                                         int32_t B, int32_t T, int32_t C, sg_stream_t stream) {
+    SG_REQUIRE(patches && cls && pos && out, "sg_clip_embed_patches: null pointer");
+    SG_REQUIRE(B > 0 && T > 1 && C > 0 && C % 4 == 0 && ldp % 4 == 0 && ldp >= C && ldo % 4 == 0 && ldo >= C,
+               "sg_clip_embed_patches: bad shape B=%d T=%d C=%d", B, T, C);
+    SG_REQUIRE(sg_aligned16(patches) && sg_aligned16(cls) && sg_aligned16(pos) && sg_aligned16(out), "sg_clip_embed_patches: 16-byte alignment");
+    const long total = (long)B * T * (C / 4);
+    const int blocks = (int)(total / 256 + 1 < 65536 ? total / 256 + 1 : 65536);
+    hipLaunchKernelGGL(clip_embed_patches_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, patches, (long)ldp, cls, pos, out, (long)ldo,
+                       B * T, T, C);
+    SG_CHECK_LAUNCH("sg_clip_embed_patches_f32");
     return SG_OK;
 }

@@ -2,9 +2,10 @@
 
   ClipTextEngine   CLIPTextModel.forward        /root/reference/model/pipeline.py:137,183; train_StorySalon_stage2.py:283-302
   VaeEngine        AutoencoderKL.encode/decode  /root/reference/model/pipeline.py:198-205,392,401; train_StorySalon_stage2.py:281-288
+  ClipVisionEngine CLIPVisionModelWithProjection over float images: the image tower of CLIP-I / CLIP-T scoring (clip_score.py)
 
 Both are eager launch sequences over the UNet's kernels (sg_gemm_f16, sg_conv3x3_nhwc_f16, sg_groupnorm_nhwc_f16, sg_layernorm_f16,
-sg_conv_in/out_f16, sg_pad_cast_f16) plus the five small kernels of csrc/encoders.hip; they run once per call of the pipeline, not per
+sg_conv_in/out_f16, sg_pad_cast_f16) plus the small kernels of csrc/encoders.hip; they run once per call of the pipeline, not per
 denoising step, so they are not captured into graphs.  Activations are channels-last; the residual stream is fp32, every MFMA operand
 fp16 — the UNet engine's conventions.  Parity: tests/test_encoders_gpu.py against oracle/encoders_oracle.py (CLIP pinned to
 transformers, the VAE restated from diffusers 0.13.1).  There is no CPU path: importing this module loads libstorygen_hip.so.
@@ -35,27 +36,31 @@ def _count(sd: SD, prefix: str) -> int:
 
 
 # ================================================================================================================== CLIP
-class ClipTextEngine:
-    """CLIP text transformer (pre-LN, causal, quick_gelu) — transformers 4.27.4 CLIPTextTransformer."""
+CLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)       # the `clip` package's Normalize() constants
+CLIP_IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
 
-    def __init__(self, state_dict: SD, device, heads: int = 12, eps: float = 1e-5, hidden_act: str = "quick_gelu"):
-        sd = {k[len("text_model."):] if k.startswith("text_model.") else k: v for k, v in state_dict.items()}
+
+def check_clip_dims(who: str, hidden: int, heads: int, tokens: int) -> None:
+    """The limits of sg_attn_small_f16 / sg_gemm_f16 for a CLIP tower: raises ValueError before anything touches the device."""
+    if heads <= 0 or hidden % heads or hidden // heads > 64 or hidden % 8:
+        raise ValueError(f"{who}: hidden size {hidden} / {heads} heads is outside sg_attn_small_f16 (head dim <= 64)")
+    if tokens > 128:
+        raise ValueError(f"{who}: {tokens} tokens exceed sg_attn_small_f16's 128 (ViT-H/14, 257 tokens of head dim 80, is out of scope)")
+
+
+class _ClipLayers:
+    """The pre-LN transformer layers both CLIP towers share (transformers CLIPEncoder): weights of `encoder.layers.*` and the launch
+    sequence of one pass over them.  The residual stream is fp32, every MFMA operand fp16."""
+
+    def __init__(self, sd: SD, dev: torch.device, heads: int, eps: float, hidden_act: str, who: str):
         if hidden_act not in ("quick_gelu", "gelu"):
-            raise ValueError(f"ClipTextEngine: unsupported hidden_act {hidden_act!r}")
-        self.dev = torch.device(device)
-        self.heads, self.eps = heads, eps
+            raise ValueError(f"{who}: unsupported hidden_act {hidden_act!r}")
+        self.dev, self.heads, self.eps = dev, heads, eps
         self.act = ops.ACT_QUICK_GELU if hidden_act == "quick_gelu" else ops.ACT_GELU
 
-        def d32(name):
-            return sd[name].detach().to(self.dev, F32).contiguous()
-
         def d16(t):
-            return t.detach().to(self.dev, F32).to(F16).contiguous()
+            return t.detach().to(dev, F32).to(F16).contiguous()
 
-        self.tok, self.pos = d32("embeddings.token_embedding.weight"), d32("embeddings.position_embedding.weight")
-        self.vocab, self.C = self.tok.shape
-        if self.C % heads or self.C // heads > 64 or self.C % 8:
-            raise ValueError(f"ClipTextEngine: hidden size {self.C} / {heads} heads is outside sg_attn_small_f16 (head dim <= 64)")
         self.layers = []
         for i in range(_count(sd, "encoder.layers.")):
             p = f"encoder.layers.{i}."
@@ -68,9 +73,59 @@ class ClipTextEngine:
                 wo=d16(sd[a + "out_proj.weight"]), bo=d16(sd[a + "out_proj.bias"]),
                 w1=d16(sd[p + "mlp.fc1.weight"]), b1=d16(sd[p + "mlp.fc1.bias"]),
                 w2=d16(sd[p + "mlp.fc2.weight"]), b2=d16(sd[p + "mlp.fc2.bias"])))
-        self.lnf = (d16(sd["final_layer_norm.weight"]), d16(sd["final_layer_norm.bias"]))
         self.inner = self.layers[0]["w1"].shape[0]
-        self.ws = ops.new_workspace(64 << 20, self.dev)
+        self.ws = ops.new_workspace(64 << 20, dev)
+
+    def run(self, x: torch.Tensor, xo: torch.Tensor, B: int, T: int, causal: bool, key_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The first layer reads the stream x [B*T, C] (fp32, or the fp16 output of a LayerNorm), every layer leaves its result in the fp32
+        stream xo (which may be x itself).  Returns an fp16 [B*T, C] scratch buffer for the caller's final LayerNorm."""
+        M, C = xo.shape
+        H, dev = self.heads, self.dev
+        x2 = torch.empty_like(xo)
+        h16 = torch.empty(M, C, dtype=F16, device=dev)
+        qkv = torch.empty(M, 3 * C, dtype=F16, device=dev)
+        a16 = torch.empty(M, C, dtype=F16, device=dev)
+        u16 = torch.empty(M, self.inner, dtype=F16, device=dev)
+        q3 = qkv.view(B, T, 3 * C)
+        scale = (C // H) ** -0.5
+        for L in self.layers:
+            ops.layernorm(x, L["ln1"][0], L["ln1"][1], h16, self.eps)
+            ops.gemm(h16, L["wqkv"], qkv, bias=L["bqkv"], workspace=self.ws)
+            ops.attention_small(q3[:, :, :C], q3[:, :, C:2 * C], q3[:, :, 2 * C:], a16.view(B, T, C), H, scale, causal, key_bias)
+            ops.gemm(a16, L["wo"], x2, bias=L["bo"], res1=x, workspace=self.ws)
+            ops.layernorm(x2, L["ln2"][0], L["ln2"][1], h16, self.eps)
+            ops.gemm(h16, L["w1"], u16, bias=L["b1"], workspace=self.ws)
+            ops.act_rows(u16, self.act)
+            ops.gemm(u16, L["w2"], xo, bias=L["b2"], res1=x2, workspace=self.ws)
+            x = xo
+        return h16
+
+
+class ClipTextEngine:
+    """CLIP text transformer (pre-LN, causal, quick_gelu) — transformers 4.27.4 CLIPTextTransformer."""
+
+    def __init__(self, state_dict: SD, device, heads: int = 12, eps: float = 1e-5, hidden_act: str = "quick_gelu"):
+        sd = {k[len("text_model."):] if k.startswith("text_model.") else k: v for k, v in state_dict.items()}
+        if hidden_act not in ("quick_gelu", "gelu"):
+            raise ValueError(f"ClipTextEngine: unsupported hidden_act {hidden_act!r}")
+        self.dev = torch.device(device)
+        self.heads, self.eps = heads, eps
+
+        def d32(name):
+            return sd[name].detach().to(self.dev, F32).contiguous()
+
+        def d16(t):
+            return t.detach().to(self.dev, F32).to(F16).contiguous()
+
+        self.tok, self.pos = d32("embeddings.token_embedding.weight"), d32("embeddings.position_embedding.weight")
+        self.vocab, self.C = self.tok.shape
+        if self.C % heads or self.C // heads > 64 or self.C % 8:
+            raise ValueError(f"ClipTextEngine: hidden size {self.C} / {heads} heads is outside sg_attn_small_f16 (head dim <= 64)")
+        self.stack = _ClipLayers(sd, self.dev, heads, eps, hidden_act, "ClipTextEngine")
+        self.layers, self.inner, self.ws, self.act = self.stack.layers, self.stack.inner, self.stack.ws, self.stack.act
+        self.lnf = (d16(sd["final_layer_norm.weight"]), d16(sd["final_layer_norm.bias"]))
+        # CLIPTextModelWithProjection's head, when the checkpoint has one (CLIP-T scoring)
+        self.proj = d16(sd["text_projection.weight"]) if "text_projection.weight" in sd else None
 
     def __call__(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """input_ids [B,T] -> (last_hidden_state fp32 [B,T,C], pooled fp32 [B,C]); T <= 128 and <= the position table."""
@@ -86,30 +141,93 @@ class ClipTextEngine:
         key_bias = None
         if attention_mask is not None:
             key_bias = ((1.0 - attention_mask.detach().to(self.dev, F32)) * torch.finfo(F32).min).contiguous()
-        C, M, H = self.C, B * T, self.heads
+        C, M = self.C, B * T
         dev = self.dev
         x = torch.empty(M, C, dtype=F32, device=dev)
-        x2 = torch.empty_like(x)
-        h16 = torch.empty(M, C, dtype=F16, device=dev)
-        qkv = torch.empty(M, 3 * C, dtype=F16, device=dev)
-        a16 = torch.empty(M, C, dtype=F16, device=dev)
-        u16 = torch.empty(M, self.inner, dtype=F16, device=dev)
         ops.embed_tokens(ids, self.tok, self.pos, x, T)
-        q3 = qkv.view(B, T, 3 * C)
-        scale = (C // H) ** -0.5
-        for L in self.layers:
-            ops.layernorm(x, L["ln1"][0], L["ln1"][1], h16, self.eps)
-            ops.gemm(h16, L["wqkv"], qkv, bias=L["bqkv"], workspace=self.ws)
-            ops.attention_small(q3[:, :, :C], q3[:, :, C:2 * C], q3[:, :, 2 * C:], a16.view(B, T, C), H, scale, True, key_bias)
-            ops.gemm(a16, L["wo"], x2, bias=L["bo"], res1=x, workspace=self.ws)
-            ops.layernorm(x2, L["ln2"][0], L["ln2"][1], h16, self.eps)
-            ops.gemm(h16, L["w1"], u16, bias=L["b1"], workspace=self.ws)
-            ops.act_rows(u16, self.act)
-            ops.gemm(u16, L["w2"], x, bias=L["b2"], res1=x2, workspace=self.ws)
+        h16 = self.stack.run(x, x, B, T, True, key_bias)
         ops.layernorm(x, self.lnf[0], self.lnf[1], h16, self.eps)
         hidden = h16.view(B, T, C).float()
         pooled = hidden[torch.arange(B, device=dev), ids_host.argmax(dim=-1).to(dev)]
         return hidden, pooled
+
+    def project(self, pooled: torch.Tensor) -> torch.Tensor:
+        """text_projection(pooled) -> fp32 [B, projection_dim] (CLIPTextModelWithProjection.text_embeds).  `pooled` is the second value
+        __call__ returns: fp16 values held in fp32, so the cast back to the GEMM's operand type is exact."""
+        if self.proj is None:
+            raise KeyError("ClipTextEngine.project: the state dict has no text_projection.weight")
+        out = torch.empty(pooled.shape[0], self.proj.shape[0], dtype=F32, device=self.dev)
+        return ops.gemm(pooled.to(self.dev, F16).contiguous(), self.proj, out, workspace=self.ws)
+
+
+class ClipVisionEngine:
+    """CLIP image tower with its projection head — transformers CLIPVisionTransformer + visual_projection (ViT-B/32 class: at most 128
+    tokens, head dim <= 64), fed by sg_clip_patchify_f16: float images of any size in, (image_embeds, last_hidden_state) out."""
+
+    def __init__(self, state_dict: SD, device, heads: int = 12, eps: float = 1e-5, hidden_act: str = "quick_gelu",
+                 image_size: Optional[int] = None):
+        sd = {k[len("vision_model."):] if k.startswith("vision_model.") else k: v for k, v in state_dict.items()}
+        wp = sd["embeddings.patch_embedding.weight"]                       # [C, 3, ps, ps]
+        pos = sd["embeddings.position_embedding.weight"]                   # [T, C]
+        self.C, self.ps, self.T = wp.shape[0], wp.shape[2], pos.shape[0]
+        grid = math.isqrt(self.T - 1)
+        if wp.dim() != 4 or wp.shape[1] != 3 or wp.shape[3] != self.ps or grid * grid != self.T - 1 or grid == 0:
+            raise ValueError(f"ClipVisionEngine: patch weight {tuple(wp.shape)} / {self.T} positions are not a square grid of RGB patches")
+        self.S = grid * self.ps
+        if image_size is not None and image_size != self.S:
+            raise ValueError(f"ClipVisionEngine: image_size {image_size} does not match {grid} x {grid} patches of {self.ps}")
+        check_clip_dims("ClipVisionEngine", self.C, heads, self.T)
+        if (3 * self.ps * self.ps) % 8:
+            raise ValueError(f"ClipVisionEngine: 3 * patch_size^2 = {3 * self.ps * self.ps} must be a multiple of 8")
+        self.pdim = sd["visual_projection.weight"].shape[0]
+        if self.pdim % 8:
+            raise ValueError(f"ClipVisionEngine: projection_dim {self.pdim} must be a multiple of 8")
+        self.dev = torch.device(device)
+        self.heads, self.eps = heads, eps
+
+        def d16(t):
+            return t.detach().to(self.dev, F32).to(F16).contiguous()
+
+        self.wp = d16(wp.reshape(self.C, 3 * self.ps * self.ps))           # (c, dy, dx) columns: the patchify kernel's order
+        self.cls = sd["embeddings.class_embedding"].detach().to(self.dev, F32).contiguous()
+        self.pos = pos.detach().to(self.dev, F32).contiguous()
+        self.pre = (d16(sd["pre_layrnorm.weight"]), d16(sd["pre_layrnorm.bias"]))
+        self.post = (d16(sd["post_layernorm.weight"]), d16(sd["post_layernorm.bias"]))
+        self.proj = d16(sd["visual_projection.weight"])
+        self.stack = _ClipLayers(sd, self.dev, heads, eps, hidden_act, "ClipVisionEngine")
+        self.ws = self.stack.ws
+
+    def __call__(self, images: torch.Tensor, in_scale: float = 1.0, in_shift: float = 0.0, mean=CLIP_IMAGE_MEAN,
+                 std=CLIP_IMAGE_STD) -> Tuple[torch.Tensor, torch.Tensor]:
+        """images float NCHW [B,3,H,W] of any size, values v with in_scale * v + in_shift in [0, 1] -> (image_embeds fp32 [B, projection_dim],
+        last_hidden_state fp32 [B,T,C]).  Resize, centre crop and normalisation are the `clip` package's preprocessing."""
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError(f"ClipVisionEngine: expected [B,3,H,W], got {tuple(images.shape)}")
+        dev, C, T, K = self.dev, self.C, self.T, 3 * self.ps * self.ps
+        B = images.shape[0]
+        img = images.detach().to(dev, F32).contiguous()
+        a16 = torch.empty(B * (T - 1), K, dtype=F16, device=dev)
+        ops.clip_patchify(img, a16, self.S, self.ps, mean, std, in_scale, in_shift)
+        pe = torch.empty(B * (T - 1), C, dtype=F32, device=dev)
+        ops.gemm(a16, self.wp, pe, workspace=self.ws)
+        e = torch.empty(B * T, C, dtype=F32, device=dev)
+        ops.clip_embed_patches(pe, self.cls, self.pos, e, T)
+        h0 = torch.empty(B * T, C, dtype=F16, device=dev)
+        ops.layernorm(e, self.pre[0], self.pre[1], h0, self.eps)          # pre_layrnorm: the stream the first layer reads and adds to
+        x = torch.empty(B * T, C, dtype=F32, device=dev)
+        self.stack.run(h0, x, B, T, False)
+        p16 = torch.empty(B, C, dtype=F16, device=dev)
+        ops.layernorm(x.view(B, T * C)[:, :C], self.post[0], self.post[1], p16, self.eps)      # post_layernorm on the class rows
+        embeds = torch.empty(B, self.pdim, dtype=F32, device=dev)
+        ops.gemm(p16, self.proj, embeds, workspace=self.ws)
+        return embeds, x.view(B, T, C)
+
+    def encode_pixels(self, pixel_values: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """CLIPVisionModelWithProjection.forward(pixel_values): already preprocessed [B,3,S,S] input, cut into patches as it is (the resampling
+        weights of an S x S image are exactly 1 and 0)."""
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, self.S, self.S):
+            raise ValueError(f"ClipVisionEngine: pixel_values must be [B,3,{self.S},{self.S}], got {tuple(pixel_values.shape)}")
+        return self(pixel_values, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0))
 
 
 # =================================================================================================================== VAE
@@ -410,6 +528,27 @@ def clip_text_param_shapes(vocab_size: int = 49408, hidden_size: int = 768, inte
         out[p + "mlp.fc2.weight"], out[p + "mlp.fc2.bias"] = (C, I), (C,)
         out[p + "layer_norm2.weight"], out[p + "layer_norm2.bias"] = (C,), (C,)
     out["text_model.final_layer_norm.weight"], out["text_model.final_layer_norm.bias"] = (C,), (C,)
+    return out
+
+
+def clip_vision_param_shapes(hidden_size: int = 768, intermediate_size: int = 3072, num_hidden_layers: int = 12, image_size: int = 224,
+                             patch_size: int = 32, projection_dim: int = 512) -> Dict[str, Tuple[int, ...]]:
+    """Names and shapes of transformers' CLIPVisionModelWithProjection parameters (defaults: ViT-B/32)."""
+    C, I = hidden_size, intermediate_size
+    out = {"vision_model.embeddings.class_embedding": (C,),
+           "vision_model.embeddings.patch_embedding.weight": (C, 3, patch_size, patch_size),
+           "vision_model.embeddings.position_embedding.weight": ((image_size // patch_size) ** 2 + 1, C),
+           "vision_model.pre_layrnorm.weight": (C,), "vision_model.pre_layrnorm.bias": (C,)}
+    for i in range(num_hidden_layers):
+        p = f"vision_model.encoder.layers.{i}."
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            out[f"{p}self_attn.{n}.weight"], out[f"{p}self_attn.{n}.bias"] = (C, C), (C,)
+        out[p + "layer_norm1.weight"], out[p + "layer_norm1.bias"] = (C,), (C,)
+        out[p + "mlp.fc1.weight"], out[p + "mlp.fc1.bias"] = (I, C), (I,)
+        out[p + "mlp.fc2.weight"], out[p + "mlp.fc2.bias"] = (C, I), (C,)
+        out[p + "layer_norm2.weight"], out[p + "layer_norm2.bias"] = (C,), (C,)
+    out["vision_model.post_layernorm.weight"], out["vision_model.post_layernorm.bias"] = (C,), (C,)
+    out["visual_projection.weight"] = (projection_dim, C)
     return out
 
 

@@ -1,4 +1,4 @@
-"""Drop-in `AutoencoderKL` and `CLIPTextModel` on the HIP engines of storygen_amd/encoders.py.
+"""Drop-in `AutoencoderKL`, `CLIPTextModel` and `CLIPVisionModelWithProjection` on the HIP engines of storygen_amd/encoders.py.
 
 They mirror what the reference's scripts and pipeline touch, nothing more:
 
@@ -8,6 +8,8 @@ They mirror what the reference's scripts and pipeline touch, nothing more:
   CLIPTextModel.from_pretrained(path, subfolder="text_encoder")    inference.py:45, train_StorySalon_stage2.py:141
   text_encoder(input_ids, attention_mask=mask)[0]                  model/pipeline.py:137,183; train_StorySalon_stage2.py:283,302
   text_encoder.config.use_attention_mask                           model/pipeline.py:128-135
+  CLIPVisionModelWithProjection(pixel_values).image_embeds          the image tower of the evaluation's CLIP-I / CLIP-T scores
+                                                                    (ViT-B/32 class; storygen_amd/clip_score.py feeds it raw frames)
 
 Weights keep the third-party packages' names and layouts (diffusers 0.13.1 AutoencoderKL, transformers CLIPTextModel), so their
 checkpoints load unchanged; `from_torch(module)` adopts an already-constructed torch module of either package.  Inference only (the
@@ -21,7 +23,8 @@ from typing import Dict, Optional
 
 import torch
 
-from ..encoders import ClipTextEngine, VaeEngine, clip_text_param_shapes, init_state, vae_param_shapes
+from ..encoders import (ClipTextEngine, ClipVisionEngine, VaeEngine, check_clip_dims, clip_text_param_shapes, clip_vision_param_shapes, init_state,
+                        vae_param_shapes)
 from .unet_2d_condition import CONFIG_NAME, SAFETENSORS_NAME, WEIGHTS_NAME, FrozenConfig
 
 SD = Dict[str, torch.Tensor]
@@ -334,5 +337,102 @@ class CLIPTextModel(_HipModule):
             raise NotImplementedError("CLIPTextModel: position_ids / output_attentions / output_hidden_states are not supported")
         hidden, pooled = self._eng()(input_ids, attention_mask)
         return CLIPTextModelOutput(hidden.to(self.dtype), pooled.to(self.dtype))
+
+    __call__ = forward
+
+
+# ----------------------------------------------------------------------------------------------------------- CLIP image tower
+CLIP_VISION_DEFAULTS = OrderedDict(hidden_size=768, intermediate_size=3072, projection_dim=512, num_hidden_layers=12, num_attention_heads=12,
+                                   num_channels=3, image_size=224, patch_size=32, hidden_act="quick_gelu", layer_norm_eps=1e-5,
+                                   attention_dropout=0.0, initializer_range=0.02, initializer_factor=1.0, model_type="clip_vision_model")
+
+
+def check_clip_vision_config(cfg, who: str = "CLIPVisionModelWithProjection") -> None:
+    """Refuses, on the host, what the kernels cannot run: a patch grid that does not tile the image, more than 128 tokens or a head dim above
+    64 (ViT-H/14), an activation other than quick_gelu / gelu."""
+    S, ps = int(cfg["image_size"]), int(cfg["patch_size"])
+    if cfg.get("num_channels", 3) != 3:
+        raise ValueError(f"{who}: num_channels must be 3")
+    if S <= 0 or ps <= 0 or S % ps:
+        raise ValueError(f"{who}: image_size {S} is not a multiple of patch_size {ps}")
+    check_clip_dims(who, int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), (S // ps) ** 2 + 1)
+    if (3 * ps * ps) % 8 or int(cfg["projection_dim"]) % 8:
+        raise ValueError(f"{who}: 3 * patch_size^2 and projection_dim must be multiples of 8")
+    if cfg["hidden_act"] not in ("quick_gelu", "gelu"):
+        raise NotImplementedError(f"{who}: hidden_act {cfg['hidden_act']!r}")
+
+
+class CLIPVisionModelOutput:
+    """CLIPVisionModelOutput as scoring code reads it: `.image_embeds` [B, projection_dim], `.last_hidden_state` [B, T, C]."""
+
+    def __init__(self, image_embeds, last_hidden_state):
+        self.image_embeds, self.last_hidden_state = image_embeds, last_hidden_state
+
+    def __getitem__(self, i):
+        return (self.image_embeds, self.last_hidden_state)[i]
+
+
+class CLIPVisionModelWithProjection(_HipModule):
+    def __init__(self, config: Optional[dict] = None, seed: int = 0, **kwargs):
+        cfg = OrderedDict(CLIP_VISION_DEFAULTS)
+        raw = dict(config or {})
+        raw.update(kwargs)
+        if "vision_config" in raw and isinstance(raw["vision_config"], dict):   # a full CLIPModel config
+            raw = dict(raw["vision_config"], projection_dim=raw.get("projection_dim", raw["vision_config"].get("projection_dim", 512)))
+        cfg.update({k: v for k, v in raw.items() if k in CLIP_VISION_DEFAULTS})
+        check_clip_vision_config(cfg)
+        self._config = FrozenConfig(cfg).freeze()
+        self._shapes = clip_vision_param_shapes(cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"], cfg["image_size"],
+                                                cfg["patch_size"], cfg["projection_dim"])
+        self._sd: SD = init_state(self._shapes, seed, embed_std=cfg["initializer_range"])
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_path: str, subfolder: Optional[str] = None, torch_dtype: Optional[torch.dtype] = None,
+                        **kwargs) -> "CLIPVisionModelWithProjection":
+        folder = os.path.join(pretrained_model_path, subfolder or "")
+        with open(os.path.join(folder, CONFIG_NAME)) as f:
+            model = cls(json.load(f))
+        model.load_state_dict(_load_weights(folder, CLIP_WEIGHTS), strict=False)
+        return model.to(torch_dtype) if torch_dtype is not None else model
+
+    @classmethod
+    def from_torch(cls, module) -> "CLIPVisionModelWithProjection":
+        """Adopt a constructed transformers CLIPVisionModelWithProjection."""
+        model = cls(module.config.to_dict() if hasattr(module.config, "to_dict") else dict(module.config))
+        model.load_state_dict(module.state_dict(), strict=False)
+        p = next(iter(module.state_dict().values()))
+        return model.to(p.device, p.dtype)
+
+    def load_state_dict(self, state_dict: SD, strict: bool = True):
+        """transformers names (`vision_model.*`, `visual_projection.weight`); a full CLIPModel checkpoint loads with strict=False.  The
+        non-parameter `position_ids` buffer of old checkpoints is ignored."""
+        sd = {k: v for k, v in state_dict.items() if not k.endswith("position_ids")}
+        missing = [k for k in self._shapes if k not in sd]
+        if missing:
+            raise RuntimeError(f"CLIPVisionModelWithProjection.load_state_dict: missing {missing[:4]} (+{max(0, len(missing) - 4)} more)")
+        self._adopt(sd, self._shapes, strict)
+
+    def save_pretrained(self, save_directory: str, safe_serialization: bool = False, **kwargs):
+        self._save(save_directory, "CLIPVisionModelWithProjection", CLIP_WEIGHTS[1], CLIP_WEIGHTS[0], safe_serialization,
+                   {"architectures": ["CLIPVisionModelWithProjection"]})
+
+    def _eng(self) -> ClipVisionEngine:
+        if self._engine is None:
+            if self.device.type != "cuda":
+                raise RuntimeError("CLIPVisionModelWithProjection: move the model to the HIP device first (.to('cuda')); there is no CPU path")
+            c = self._config
+            self._engine = ClipVisionEngine(self._sd, self.device, heads=c["num_attention_heads"], eps=c["layer_norm_eps"],
+                                            hidden_act=c["hidden_act"], image_size=c["image_size"])
+        return self._engine
+
+    def forward(self, pixel_values: torch.Tensor, output_attentions=None, output_hidden_states=None, return_dict=None):
+        """pixel_values [B, 3, image_size, image_size], already resized and normalised (what a CLIPImageProcessor returns)."""
+        if output_attentions or output_hidden_states:
+            raise NotImplementedError("CLIPVisionModelWithProjection: output_attentions / output_hidden_states are not supported")
+        S = self._config["image_size"]
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, S, S):
+            raise ValueError(f"CLIPVisionModelWithProjection: pixel_values must be [B,3,{S},{S}], got {tuple(pixel_values.shape)}")
+        embeds, hidden = self._eng().encode_pixels(pixel_values)
+        return CLIPVisionModelOutput(embeds.to(self.dtype), hidden.to(self.dtype))
 
     __call__ = forward

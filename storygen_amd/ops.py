@@ -655,6 +655,45 @@ def gaussian_sample(mean: torch.Tensor, logvar: Optional[torch.Tensor], noise: O
     return out
 
 
+def clip_resize_geometry(H: int, W: int, S: int) -> tuple:
+    """(resized H, resized W, top, left) of torchvision's Resize(S) + CenterCrop(S) on an H x W image (sg_clip_resize_geometry; host only)."""
+    g = (C.c_int32 * 4)()
+    check(lib.sg_clip_resize_geometry(int(H), int(W), int(S), g), "sg_clip_resize_geometry")
+    return tuple(g)
+
+
+def clip_patchify(x: torch.Tensor, out: torch.Tensor, S: int, ps: int, mean, std, in_scale: float = 1.0, in_shift: float = 0.0) -> torch.Tensor:
+    """x fp32 NCHW [B,3,H,W] -> out fp16 [B * (S/ps)^2, 3*ps*ps]: (in_scale * x + in_shift) resized (antialiased bicubic) so that the shorter
+    side is S, centre-cropped to S x S, normalised with the per-channel mean / std (3 floats each) and cut into patches, columns (c, dy, dx)."""
+    _f32(x, "x"), _f16(out, "out")
+    if x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+        raise ValueError(f"clip_patchify: x must be a contiguous [B,3,H,W] tensor, got {tuple(x.shape)}")
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("clip_patchify: mean and std hold one value per channel")
+    B, _, H, W = x.shape
+    if S <= 0 or ps <= 0 or S % ps:
+        raise ValueError(f"clip_patchify: crop size {S} is not a multiple of patch size {ps}")
+    if out.dim() != 2 or tuple(out.shape) != (B * (S // ps) ** 2, 3 * ps * ps):
+        raise ValueError(f"clip_patchify: out must be [{B * (S // ps) ** 2},{3 * ps * ps}], got {tuple(out.shape)}")
+    m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    check(lib.sg_clip_patchify_f16(x.data_ptr(), B, H, W, float(in_scale), float(in_shift), m, s, int(S), int(ps), out.data_ptr(),
+                                   _row_stride(out, "out"), _stream()), "sg_clip_patchify_f16")
+    return out
+
+
+def clip_embed_patches(patches: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, out: torch.Tensor, T: int) -> torch.Tensor:
+    """out[b*T] = cls + pos[0]; out[b*T + t] = patches[b*(T-1) + t-1] + pos[t] (fp32): CLIPVisionEmbeddings on the residual stream."""
+    _f32(patches, "patches"), _f32(cls, "cls"), _f32(pos, "pos"), _f32(out, "out")
+    Cc = out.shape[1]
+    if out.shape[0] % T or patches.shape[0] != out.shape[0] // T * (T - 1) or patches.shape[1] != Cc:
+        raise ValueError("clip_embed_patches: patches must hold T - 1 rows for every T rows of out")
+    if not cls.is_contiguous() or not pos.is_contiguous() or cls.numel() != Cc or tuple(pos.shape) != (T, Cc):
+        raise ValueError("clip_embed_patches: cls must be [C] and pos [T,C]")
+    check(lib.sg_clip_embed_patches_f32(patches.data_ptr(), _row_stride(patches, "patches"), cls.data_ptr(), pos.data_ptr(), out.data_ptr(),
+                                        _row_stride(out, "out"), out.shape[0] // T, T, Cc, _stream()), "sg_clip_embed_patches_f32")
+    return out
+
+
 def groupnorm_workspace_bytes(B: int, groups: int) -> int:
     return lib.sg_groupnorm_workspace_bytes(B, groups)
 
