@@ -75,21 +75,12 @@ FF_PROJ_MERGE = True
 LN_EPS = 1e-5         # torch.nn.LayerNorm default, as the reference constructs norm1..norm4 (model/attention.py:213-233)
 
 
-PAIR_FALLBACK_LAT = False   # development (tools/exp_determinism.py): let the unpaired form of a paired projection take the latency kernel by size
-VT_LAT_TILE = (64, 64, 4)   # development: the hint VT_LAT_FILTER applies
-VT_CHECK = None             # development: int64 device counter (see VT_LAT_FILTER)
-VT_MASK = VT_DIFF = None    # development: per-element mismatch count / last difference of the checked V^T launches
-VT_HASH = None              # development: dict(buf=[K, 4] int64, ctr=[1] int64): per hinted V^T launch the integer sums of its inputs (raw copy, LayerNorm partials) and outputs (q|k, V^T), in launch order
-VT_LAT_FILTER = None        # development: callable(prefix, consume) -> bool; with PAIR_GEMMS off, the V^T projection (columns-are-tokens fold) of the
-                            # transformers it selects is HINTED onto the latency kernel, every other unpaired projection is kept off it
-
-
 def _pair(first, second):
     if PAIR_GEMMS:
         ops.gemm_pair(first, second)
     else:       # (the projections that are paired stay off the latency kernel either way: tile hint (0, 0, -1))
         for args, kw in (first, second):
-            ops.gemm(*args, **(kw if PAIR_FALLBACK_LAT else {**kw, "tile": (0, 0, -1)}))
+            ops.gemm(*args, **{**kw, "tile": (0, 0, -1)})
 
 
 class _Resnet:
@@ -319,6 +310,35 @@ class HarvestPlan:
         return seen == {u: u for u in range(n_samples)}
 
 
+class _XfPass:
+    """What one pass through a transformer derives from the module switches, the engine and its operands: made once per call (at call
+    time: the switches are A/B knobs), read by every stage (UNetEngine._xf_*)."""
+
+    def __init__(self, eng: "UNetEngine", xf: _Xf, x: torch.Tensor, out: Optional[torch.Tensor], lvl: int, consume: bool):
+        L = self.L = eng.lv[lvl]
+        self.xf, self.x, self.out, self.lvl, self.consume, self.guard = xf, x, out, lvl, consume, eng.ln_guard
+        self.B, self.hw, self.M, self.C, self.heads = eng.B, eng.hw[lvl], x.shape[0], xf.spec.channels, xf.spec.heads
+        self.scale = xf.spec.dim_head ** -0.5
+        self.fold = LN_FOLD and self.C % 64 == 0 and self.C // 64 <= 20
+        # fused feed-forward: needs the fp32 stream (it reads h3 itself: no raw copy, no LayerNorm partials from h3's producer)
+        self.ff1 = FF_FUSED and xf.ff_pack is not None and L["h3"].dtype != F16
+        # ff.net.2 + proj_out as one GEMM (FF_PROJ_MERGE): h3's raw copy lives beside the GEGLU output in L["ffo"]
+        self.merge = FF_PROJ_MERGE and self.fold and not self.ff1 and xf.w_ffo is not None and L["h3"].dtype != F16 and out is not None
+        self.h0r, self.h1r = self.raw(L["h0"], L["ln"]), self.raw(L["h1"], L["ln4"])
+        self.h3raw = L["ffo"][:self.M, 4 * self.C:5 * self.C] if self.merge else L["ln"]
+
+    @staticmethod
+    def raw(t: torch.Tensor, buf: torch.Tensor) -> torch.Tensor:
+        return t if t.dtype == F16 else buf                      # (fp16 stream: it IS the copy)
+
+    def prod(self, t: torch.Tensor, buf: torch.Tensor, st: torch.Tensor) -> dict:
+        """With the fold, the producer of a stream tensor also writes its raw fp16 copy and the LayerNorm partials of its rows."""
+        return dict(out2=None if t.dtype == F16 else buf, ln_out=st, guard=self.guard) if self.fold else {}
+
+    def prod3(self, h3: torch.Tensor) -> dict:
+        return {} if self.ff1 else self.prod(h3, self.h3raw, self.L["lnst3"])
+
+
 class UNetEngine:
     def __init__(self, arch: UNetArch, state_dict: Optional[Dict[str, torch.Tensor]], device, batch: int, height: int,
                  width: int, n_ref: int = 0, seq_len: int = 77, splitk_workspace_mb: int = 96,
@@ -375,7 +395,6 @@ class UNetEngine:
                                          and first.attns and first.attns[0] is not None and not fp8_attention):
             raise ValueError("cfg_shared_head needs batch 3 on 2 shared context rows (the CFG main pass of one story frame), a transformer "
                              "behind the first resnet and the fp16 attention path")
-        self._shared_back = False
         self._head_checked = False
         self.fp16_block, self.fp16_resnet = (FP16_BLOCK_STREAM, FP16_RESNET_STREAM) if fp16_stream is None else map(bool, fp16_stream)
         self.wts = weights if weights is not None else EngineWeights(arch, state_dict, device)
@@ -597,6 +616,16 @@ class UNetEngine:
     def _publish(self, out: torch.Tensor, site: str, n_out: int):
         self._pstats[out.data_ptr()] = (self._stats_buf[site], self._stats_rows[site], n_out)
 
+    def _produce(self, site: str, lvl: int, n_out: int, out: torch.Tensor, launch, rows):
+        """A producer of `out` [B*hw[lvl], n_out] that may emit GroupNorm statistics: launch(statistics buffer or None) runs it, rows(buf)
+        is _stats_for's query for exactly that launch."""
+        st = self._stats_for(site, lvl, n_out, rows)
+        launch(st)
+        if st is not None:
+            self._publish(out, site, n_out)
+        else:
+            self._pstats.pop(out.data_ptr(), None)
+
     def _pstats_of(self, x: torch.Tensor) -> Optional[list]:
         """Producer statistics covering x [M, C] (one producer, or two for a channel concat [h | skip]), else None."""
         C = x.shape[1]
@@ -664,13 +693,8 @@ class UNetEngine:
             ops.groupnorm(h1.unflatten(0, (B, hw)), rn.n2g, rn.n2b, p_mid, self.groups, self.eps, True, self.ws_gn,
                           split=dict(ws=ws, splits=d1, rowbias=rb, store=False))
         else:
-            s1 = self._stats_for(r.prefix + ".conv1", lvl, r.cout,
-                                 lambda buf: ops.conv3x3_stats_rows(p_in, rn.w1, self._img(h1, lvl), stats=buf, **kw1))
-            ops.conv3x3(p_in, rn.w1, self._img(h1, lvl), stats=s1, **kw1)
-            if s1 is not None:
-                self._publish(h1, r.prefix + ".conv1", r.cout)
-            else:
-                self._pstats.pop(h1.data_ptr(), None)
+            self._produce(r.prefix + ".conv1", lvl, r.cout, h1, lambda s: ops.conv3x3(p_in, rn.w1, self._img(h1, lvl), stats=s, **kw1),
+                          lambda buf: ops.conv3x3_stats_rows(p_in, rn.w1, self._img(h1, lvl), stats=buf, **kw1))
             ops.groupnorm(h1.unflatten(0, (B, hw)), rn.n2g, rn.n2b, p_mid, self.groups, self.eps, True, self.ws_gn,
                           pstats=self._pstats_of(h1))
         if forked:
@@ -684,13 +708,8 @@ class UNetEngine:
             self._pstats.pop(out.data_ptr(), None)
             self._pending_split[out.data_ptr()] = dict(ws=ws, splits=d2, bias=rn.b2, res1=res.unflatten(0, (B, hw)), store=True)
             return
-        s2 = self._stats_for(r.prefix + ".conv2", lvl, r.cout,
-                             lambda buf: ops.conv3x3_stats_rows(p_mid, rn.w2, self._img(out, lvl), stats=buf, **kw2))
-        ops.conv3x3(p_mid, rn.w2, self._img(out, lvl), stats=s2, **kw2)
-        if s2 is not None:
-            self._publish(out, r.prefix + ".conv2", r.cout)
-        else:
-            self._pstats.pop(out.data_ptr(), None)
+        self._produce(r.prefix + ".conv2", lvl, r.cout, out, lambda s: ops.conv3x3(p_mid, rn.w2, self._img(out, lvl), stats=s, **kw2),
+                      lambda buf: ops.conv3x3_stats_rows(p_mid, rn.w2, self._img(out, lvl), stats=buf, **kw2))
 
     def _text_kv(self, xf: _Xf, lvl: int, use_cache: bool):
         """K and V^T projections of the text embeddings for attn2 (attention.py:192-199): timestep-invariant, so the
@@ -722,211 +741,189 @@ class UNetEngine:
                                                         self._buf(a.channels, self.B * self.Sp))
                 self._project_text(self.xfs[a.prefix], *bufs)
 
+    # ---- Transformer2DModel.forward (attention.py:85-128) + BasicTransformerBlock.forward (:236-302) as stages on one _XfPass: x, out,
+    # h0..h3 are the fp32 stream, everything that feeds an MFMA is fp16
     def _transformer(self, xf: _Xf, x: torch.Tensor, out: Optional[torch.Tensor], lvl: int, text: Optional[torch.Tensor],
-                     harvest: Optional[HarvestPlan], consume: bool, text_cache: bool = False, stop_after_harvest: bool = False,
-                     phase: str = "all"):
-        """Transformer2DModel.forward (attention.py:85-128) + BasicTransformerBlock.forward (:236-302).
-        x, out, h0..h3 fp32; everything that feeds an MFMA fp16.
-        phase: "front" = up to and including the query projections of the cross-attentions (everything that depends on the hidden
-        states alone), "back" = from the cross-attentions on, "all" = both (cfg_shared_head runs the front once for the three
-        CFG samples)."""
-        L, B, hw, S = self.lv[lvl], self.B, self.hw[lvl], self.S
-        M, C, heads = x.shape[0], xf.spec.channels, xf.spec.heads
-        scale = xf.spec.dim_head ** -0.5
-        ws = self.ws_split
-        h0 = L["h0"]
-        fold = LN_FOLD and C % 64 == 0 and C // 64 <= 20
-        # fused feed-forward: needs the fp32 stream (it reads h3 itself: no raw copy, no LayerNorm partials from h3's producer)
-        ff1 = FF_FUSED and xf.ff_pack is not None and L["h3"].dtype != F16
-        # with the fold, the producer of a stream tensor also writes its raw fp16 copy and the LayerNorm partials of its rows
-        raw = lambda t, buf: t if t.dtype == F16 else buf                                 # noqa: E731  (fp16 stream: it IS the copy)
-        gd = self.ln_guard
-        prod = lambda t, buf, st: dict(out2=None if t.dtype == F16 else buf, ln_out=st, guard=gd) if fold else {}   # noqa: E731
-        h0r, h1r = raw(h0, L["ln"]), raw(L["h1"], L["ln4"])
-        # ff.net.2 + proj_out as one GEMM (FF_PROJ_MERGE): h3's raw copy lives beside the GEGLU output in L["ffo"]
-        merge = FF_PROJ_MERGE and fold and not ff1 and xf.w_ffo is not None and L["h3"].dtype != F16 and out is not None
-        h3raw = L["ffo"][:M, 4 * C:5 * C] if merge else L["ln"]
-        qk, vt = L["qk"], L["vt"]
-        wp = self.ws_pair
-        att = L["att"]
-        h1 = L["h1"]
-        q2, q3buf = L["q2"], L["q"]
-        if phase != "back":
-            ops.groupnorm(x.unflatten(0, (B, hw)), xf.ng, xf.nb, L["gn"].unflatten(0, (B, hw)), self.groups, 1e-6, False,
-                          self.ws_gn, pstats=self._pstats_of(x), split=self._pending_split.pop(x.data_ptr(), None))   # :99 (eps 1e-6, :55)
-            ops.gemm(L["gn"], xf.w_in, h0, bias=xf.b_in, workspace=ws, **prod(h0, L["ln"], L["lnst0"]))   # proj_in :101
-            # --- self-attention :250-262
-            # q|k (token-major) and V^T = Wv . X^T (the attention kernel's operand layout): two GEMMs on one LayerNorm output, one launch
-            if fold and VT_LAT_FILTER is not None and not PAIR_GEMMS:      # development: bisecting by transformer
-                ops.gemm(h0r, xf.w_qk1f, qk, ln=(1, L["lnst0"], xf.c_qk1, xf.d_qk1, LN_EPS), guard=gd, tile=(0, 0, -1))
-                sel = VT_LAT_FILTER(xf.spec.prefix, consume)
-                ops.gemm(xf.w_v1f, h0r, vt, ln=(2, L["lnst0"], xf.c_v1, xf.d_v1, LN_EPS), guard=gd, tile=VT_LAT_TILE if sel else (0, 0, -1))
-                if sel and VT_HASH is not None:       # order-independent integer sums: are the INPUTS of a differing launch the same in both runs?
-                    HS = VT_HASH[bool(consume)]          # (one record per engine: the two branches of the graph run concurrently)
-                    isum = lambda t, dt: t.contiguous().view(dt).sum(dtype=torch.int64)      # noqa: E731
-                    row = torch.stack([isum(h0r, torch.int16), isum(L["lnst0"], torch.int32), isum(qk, torch.int16), isum(vt, torch.int16),
-                                       torch.full((), vt.shape[1], dtype=torch.int64, device=vt.device)])
-                    HS["buf"].index_copy_(0, HS["ctr"], row.unsqueeze(0))
-                    if "vts" in HS:                      # ... and the V^T images themselves (flattened, zero-padded to the row length), + the inputs
-                        for key, t in (("vts", vt), ("xs", h0r), ("sts", L["lnst0"])):
-                            flat = t.contiguous().reshape(1, -1)
-                            HS[key].index_copy_(0, HS["ctr"], torch.nn.functional.pad(flat, (0, HS[key].shape[1] - flat.shape[1])))
-                    HS["ctr"].add_(1)
-                if sel and VT_CHECK is not None:      # the same projection again on the 64x64-per-wave kernel; count elements that differ by more than rounding
-                    chk = torch.empty_like(vt)
-                    ops.gemm(xf.w_v1f, h0r, chk, ln=(2, L["lnst0"], xf.c_v1, xf.d_v1, LN_EPS), guard=gd, tile=(0, 0, -1))
-                    a, b = vt.float(), chk.float()
-                    bad = (a - b).abs() > 0.01 + 0.01 * b.abs()
-                    VT_CHECK.add_(bad.sum())
-                    if VT_MASK is not None and VT_MASK.shape == bad.shape:
-                        VT_MASK.add_(bad.to(VT_MASK.dtype))
-                        VT_DIFF.copy_(torch.where(bad, a - b, VT_DIFF))
-            elif fold:
-                _pair(((h0r, xf.w_qk1f, qk), dict(ln=(1, L["lnst0"], xf.c_qk1, xf.d_qk1, LN_EPS), guard=gd)),
-                      ((xf.w_v1f, h0r, vt), dict(ln=(2, L["lnst0"], xf.c_v1, xf.d_v1, LN_EPS), guard=gd)))
-            else:
-                ops.layernorm(h0, *xf.ln["norm1"], L["ln"])
-                _pair(((L["ln"], xf.w_qk1, qk), dict(workspace=ws)), ((xf.w_v1, L["ln"], vt), dict(workspace=wp)))
-            qk3 = qk.view(B, hw, 2 * C)
-            self._attention(qk3[:, :, :C], qk3[:, :, C:], vt.view(C, B, hw).permute(1, 0, 2), att.view(B, hw, C), heads, scale)
-            plans = () if harvest is None else (tuple(harvest) if isinstance(harvest, (list, tuple)) else (harvest,))
-            # feature :263.  A plan whose sample order is the context's slot order (HarvestPlan.direct) gets the feature as the second,
-            # fp16 output of this GEMM — written straight into the context buffer, which then also serves as the raw copy of h1 that the
-            # folded query projections read; any other plan is served by strided copies.
-            direct = None
-            if len(plans) == 1 and plans[0].is_direct(B, plans[0].slots_per_row or self.R):
-                c = plans[0].ctx[xf.spec.feature_key]
-                direct = c if c.dim() == 2 else c.view(-1, C)
-                assert direct.shape[0] == M, (direct.shape, M)
-            kw1 = prod(h1, L["ln4"], L["lnst1"])
-            if direct is not None:
-                kw1["out2"] = direct
-                h1r = direct
-            ops.gemm(att, xf.w_o1, h1, bias=xf.b_o1, res1=h0, workspace=ws, **kw1)
-            if harvest is not None:
-                h1b = h1.view(B, hw, C)
-                for plan in plans:
-                    ctx = plan.ctx[xf.spec.feature_key]
-                    c2d = ctx if ctx.dim() == 2 else ctx.view(-1, C)
-                    if direct is None:
-                        Rp = plan.slots_per_row or (ctx.shape[1] // hw)
-                        for src, step, row, slot, cnt in plan.ops:
-                            t0 = plan.flat_slot(row, slot, Rp) * hw
-                            dst = c2d[t0:t0 + cnt * hw].view(cnt, hw, C)
-                            ops.copy_rows(dst, h1b[plan.src_offset + src:].as_strided((cnt, hw, C), (step * hw * C, C, 1)))
-                    if plan.kv is not None:            # attn3 K / V^T of the finished context (attention.py:215-223)
-                        ki, vti = plan.kv[xf.spec.feature_key]
-                        _pair(((c2d, xf.w_k3, ki), dict(workspace=ws)), ((xf.w_v3, c2d, vti), dict(workspace=wp)))   # VT[C, slots*hw]
-                if stop_after_harvest:
-                    return
-            # --- query projections of the text cross-attention :266-277 (norm2) and the image cross-attention :281-291 (norm4): they
-            # share statistics, and both in one launch
-            if fold:
-                pass
-            elif consume:
-                ops.layernorm(h1, *xf.ln["norm2"], L["ln"], 1e-5, *xf.ln["norm4"], L["ln4"])
-            else:
-                ops.layernorm(h1, *xf.ln["norm2"], L["ln"])
-            if consume and fold:
-                _pair(((h1r, xf.w_q2f, q2), dict(ln=(1, L["lnst1"], xf.c_q2, xf.d_q2, LN_EPS), guard=gd)),
-                      ((h1r, xf.w_q3f, q3buf), dict(ln=(1, L["lnst1"], xf.c_q3, xf.d_q3, LN_EPS), guard=gd)))
-            elif consume:
-                _pair(((L["ln"], xf.w_q2, q2), dict(workspace=ws)), ((L["ln4"], xf.w_q3, q3buf), dict(workspace=wp)))
-            elif fold:
-                ops.gemm(h1r, xf.w_q2f, L["q"], ln=(1, L["lnst1"], xf.c_q2, xf.d_q2, LN_EPS), guard=gd)
-            else:
-                ops.gemm(L["ln"], xf.w_q2, L["q"], workspace=ws)
-            if phase == "front":
-                return
-        kt3, vtt3 = self._text_kv(xf, lvl, text_cache)
-        if consume:
-            # the text branch (q2 -> attn2, :266-276) and the image branch (q3 -> attn3, :281-290) write the two halves
-            # of one [M, 2C] buffer; their out-projections, biases and both residual adds (:277,291-293) are one GEMM
-            att23 = L["att23"]
-            a2v, a3v = att23[:, :C].unflatten(0, (B, hw)), att23[:, C:].unflatten(0, (B, hw))
-            shared = self._shared_back      # cfg_shared_head, first transformer: ONE query tensor for the three CFG samples
-            if shared:
-                q2q = q2[:hw].view(1, hw, C).expand(2, hw, C)
-                q3q = q3buf[:hw].view(1, hw, C).expand(2, hw, C)
-                kt3, vtt3, a2o, a3o = kt3[::2], vtt3[::2], a2v[::2], a3v[:2]       # text rows (uncond, text) -> samples 0 and 2
-            else:
-                q2q, q3q, a2o, a3o = q2.view(B, hw, C), q3buf.view(B, hw, C), a2v, a3v
-            # text + image attention as one launch when the image attention is one fp16 launch itself (else the text attention runs
-            # beside the context projections on the side stream)
-            paired = (ATTN_PAIR and self.attn3_share is not None and not self.ctx_short and not shared
-                      and not (self.fp8_attention and C == heads * 40))
-            forked = False if paired else self._fork()
-            if paired:
-                pass
-            elif forked:
-                with torch.cuda.stream(self.side):
-                    ops.attention(q2q, kt3, vtt3, a2o, heads, scale, nk=S)
-            else:
-                ops.attention(q2q, kt3, vtt3, a2o, heads, scale, nk=S)
-            ctx = self.ctx[xf.spec.feature_key]
-            ns, rows = self.ctx_short, self.ctx_rows
-            nk = self.R * hw
-            c2d = ctx if ctx.dim() == 2 else ctx.view(-1, C)
-            if self.kv_ext is not None:
-                ki, vti = self.kv_ext[xf.spec.feature_key]
-            else:
-                ki, vti = L["ki"], L["vti"]
-                _pair(((c2d, xf.w_k3, ki), dict(workspace=ws)), ((xf.w_v3, c2d, vti), dict(workspace=wp)))   # VT[C, slots*hw]
-            # K / V^T rows: `ns` short ones (hw keys) in front of rows - ns long ones (R hw keys)
-            ki3 = ki[ns * hw:].view(rows - ns, nk, C)
-            vti3 = vti[:, ns * hw:].unflatten(1, (rows - ns, nk)).permute(1, 0, 2)
-            short = None
-            if ns:
-                short = (ki[: ns * hw].view(ns, hw, C), vti[:, : ns * hw].unflatten(1, (ns, hw)).permute(1, 0, 2))
-            q3 = q3q
-            if paired:
-                ops.attention_pair((q3, ki3, vti3, a3v, None), (q2q, kt3, vtt3, a2v, S), heads, scale)
-            elif self.attn3_share is not None:    # one launch: batch b reads context row b (b < rows) or b - (B - rows)
-                self._attention(q3, ki3, vti3, a3o, heads, scale, short=short)
-            else:
-                for q0, n, c0 in self.attn3_groups:
-                    self._attention(q3[q0:q0 + n], ki3[c0:c0 + n], vti3[c0:c0 + n], a3v[q0:q0 + n], heads, scale)
-            if forked:
-                self._join()
-            if shared:      # sample 1 = (uncond text, frames): its text attention is sample 0's, its image attention sample 2 shares
-                ops.copy_rows(a2v[1:2], a2v[0:1])
-                ops.copy_rows(a3v[2:3], a3v[1:2])
-            h3 = L["h3"]
-            ops.gemm(att23, xf.w_o23, h3, bias=xf.b_o23, res1=h1, res2=h1, workspace=ws,  # (a2 + h) + (a3 + h)
-                     **({} if ff1 else prod(h3, h3raw, L["lnst3"])))
+                     harvest: Optional[HarvestPlan], consume: bool, text_cache: bool = False):
+        st = _XfPass(self, xf, x, out, lvl, consume)
+        self._xf_to_harvest(st, harvest)
+        self._xf_queries(st)
+        self._xf_back(st, text_cache)
+
+    def _xf_to_harvest(self, st: _XfPass, harvest):
+        """Everything up to and including the harvested feature (a harvest_only pass needs nothing behind it)."""
+        plans = () if harvest is None else (tuple(harvest) if isinstance(harvest, (list, tuple)) else (harvest,))
+        self._xf_entry(st)
+        self._self_projections(st, st.L["h0"], st.h0r, st.L["qk"], st.L["vt"])
+        self._xf_harvest(st, plans, self._xf_self_attention(st, plans))
+
+    def _xf_back(self, st: _XfPass, text_cache: bool, shared: bool = False):
+        """From the cross-attentions on: everything that depends on more than the hidden states (cfg_shared_head runs what comes before
+        once for the three CFG samples; shared = their ONE query tensor is still the only one)."""
+        h3 = self._xf_cross_consume(st, text_cache, shared) if st.consume else self._xf_cross_text(st, text_cache)
+        self._xf_feed_forward(st, h3)
+
+    def _xf_entry(self, st: _XfPass):
+        L, xf, x = st.L, st.xf, st.x
+        ops.groupnorm(x.unflatten(0, (st.B, st.hw)), xf.ng, xf.nb, L["gn"].unflatten(0, (st.B, st.hw)), self.groups, 1e-6, False,
+                      self.ws_gn, pstats=self._pstats_of(x), split=self._pending_split.pop(x.data_ptr(), None))   # :99 (eps 1e-6, :55)
+        ops.gemm(L["gn"], xf.w_in, L["h0"], bias=xf.b_in, workspace=self.ws_split, **st.prod(L["h0"], L["ln"], L["lnst0"]))   # proj_in :101
+
+    def _self_projections(self, st: _XfPass, h0: torch.Tensor, h0r: torch.Tensor, qk: torch.Tensor, vt: torch.Tensor):
+        """Self-attention projections :250-262: q|k (token-major) and V^T = Wv . X^T (the attention kernel's operand layout), two GEMMs on
+        one LayerNorm output, one launch.  Reads h0 — folded: its raw copy h0r and the partials L["lnst0"] — and writes qk and vt.
+        (tools/exp_determinism.py puts its instrumented variant in this method's place.)"""
+        xf, L = st.xf, st.L
+        if st.fold:
+            _pair(((h0r, xf.w_qk1f, qk), dict(ln=(1, L["lnst0"], xf.c_qk1, xf.d_qk1, LN_EPS), guard=st.guard)),
+                  ((xf.w_v1f, h0r, vt), dict(ln=(2, L["lnst0"], xf.c_v1, xf.d_v1, LN_EPS), guard=st.guard)))
         else:
-            ops.attention(L["q"].view(B, hw, C), kt3, vtt3, att.view(B, hw, C), heads, scale, nk=S)
-            h3 = L["h2"]
-            ops.gemm(att, xf.w_o2, h3, bias=xf.b_o2, res1=h1, workspace=ws, **({} if ff1 else prod(h3, h3raw, L["lnst3"])))   # :277,295
-        # --- feed-forward :298-300
+            ops.layernorm(h0, *xf.ln["norm1"], L["ln"])
+            _pair(((L["ln"], xf.w_qk1, qk), dict(workspace=self.ws_split)), ((xf.w_v1, L["ln"], vt), dict(workspace=self.ws_pair)))
+
+    def _xf_self_attention(self, st: _XfPass, plans: tuple) -> Optional[torch.Tensor]:
+        """Self-attention and its out-projection + residual -> h1, the feature :263.  A plan whose sample order is the context's slot
+        order (HarvestPlan.direct) gets the feature as the second, fp16 output of that GEMM — written straight into the context buffer,
+        which then also serves as the raw copy of h1 that the folded query projections read.  Returns that buffer, or None: any other
+        plan is served by strided copies (_xf_harvest)."""
+        xf, L, B, hw, C = st.xf, st.L, st.B, st.hw, st.C
+        qk3 = L["qk"].view(B, hw, 2 * C)
+        self._attention(qk3[:, :, :C], qk3[:, :, C:], L["vt"].view(C, B, hw).permute(1, 0, 2), L["att"].view(B, hw, C), st.heads, st.scale)
+        direct = None
+        if len(plans) == 1 and plans[0].is_direct(B, plans[0].slots_per_row or self.R):
+            c = plans[0].ctx[xf.spec.feature_key]
+            direct = c if c.dim() == 2 else c.view(-1, C)
+            assert direct.shape[0] == st.M, (direct.shape, st.M)
+        kw1 = st.prod(L["h1"], L["ln4"], L["lnst1"])
+        if direct is not None:
+            kw1["out2"] = st.h1r = direct
+        ops.gemm(L["att"], xf.w_o1, L["h1"], bias=xf.b_o1, res1=L["h0"], workspace=self.ws_split, **kw1)
+        return direct
+
+    def _xf_harvest(self, st: _XfPass, plans: tuple, direct: Optional[torch.Tensor]):
+        """h1 into the context buffers of the plans that did not get it directly (one strided copy per op), and the attn3 K / V^T of
+        each context this finishes (HarvestPlan.kv; attention.py:215-223)."""
+        xf, hw, C = st.xf, st.hw, st.C
+        h1b = st.L["h1"].view(st.B, hw, C)
+        for plan in plans:
+            ctx = plan.ctx[xf.spec.feature_key]
+            c2d = ctx if ctx.dim() == 2 else ctx.view(-1, C)
+            if direct is None:
+                Rp = plan.slots_per_row or (ctx.shape[1] // hw)
+                for src, step, row, slot, cnt in plan.ops:
+                    t0 = plan.flat_slot(row, slot, Rp) * hw
+                    dst = c2d[t0:t0 + cnt * hw].view(cnt, hw, C)
+                    ops.copy_rows(dst, h1b[plan.src_offset + src:].as_strided((cnt, hw, C), (step * hw * C, C, 1)))
+            if plan.kv is not None:
+                ki, vti = plan.kv[xf.spec.feature_key]
+                _pair(((c2d, xf.w_k3, ki), dict(workspace=self.ws_split)), ((xf.w_v3, c2d, vti), dict(workspace=self.ws_pair)))   # VT[C, slots*hw]
+
+    def _xf_queries(self, st: _XfPass):
+        """Query projections of the text cross-attention :266-277 (norm2) and, in a main pass, the image cross-attention :281-291
+        (norm4): they share statistics, and both in one launch."""
+        xf, L, h1, h1r, gd, ws = st.xf, st.L, st.L["h1"], st.h1r, st.guard, self.ws_split
+        if st.consume and st.fold:
+            _pair(((h1r, xf.w_q2f, L["q2"]), dict(ln=(1, L["lnst1"], xf.c_q2, xf.d_q2, LN_EPS), guard=gd)),
+                  ((h1r, xf.w_q3f, L["q"]), dict(ln=(1, L["lnst1"], xf.c_q3, xf.d_q3, LN_EPS), guard=gd)))
+        elif st.consume:
+            ops.layernorm(h1, *xf.ln["norm2"], L["ln"], 1e-5, *xf.ln["norm4"], L["ln4"])
+            _pair(((L["ln"], xf.w_q2, L["q2"]), dict(workspace=ws)), ((L["ln4"], xf.w_q3, L["q"]), dict(workspace=self.ws_pair)))
+        elif st.fold:
+            ops.gemm(h1r, xf.w_q2f, L["q"], ln=(1, L["lnst1"], xf.c_q2, xf.d_q2, LN_EPS), guard=gd)
+        else:
+            ops.layernorm(h1, *xf.ln["norm2"], L["ln"])
+            ops.gemm(L["ln"], xf.w_q2, L["q"], workspace=ws)
+
+    def _ctx_kv(self, st: _XfPass):
+        """attn3's K / V^T of the image context — projected here unless a reference pass left them (kv_ext) — as (K [rows - ns, R hw, C],
+        VT [rows - ns, C, R hw], short): `ns` short rows (hw keys each, `short` = their (K, VT) or None) in front of the long ones."""
+        xf, L, hw, C = st.xf, st.L, st.hw, st.C
+        if self.kv_ext is not None:
+            ki, vti = self.kv_ext[xf.spec.feature_key]
+        else:
+            ctx = self.ctx[xf.spec.feature_key]
+            c2d = ctx if ctx.dim() == 2 else ctx.view(-1, C)
+            ki, vti = L["ki"], L["vti"]
+            _pair(((c2d, xf.w_k3, ki), dict(workspace=self.ws_split)), ((xf.w_v3, c2d, vti), dict(workspace=self.ws_pair)))   # VT[C, slots*hw]
+        ns, rows, nk = self.ctx_short, self.ctx_rows, self.R * hw
+        short = (ki[: ns * hw].view(ns, hw, C), vti[:, : ns * hw].unflatten(1, (ns, hw)).permute(1, 0, 2)) if ns else None
+        return ki[ns * hw:].view(rows - ns, nk, C), vti[:, ns * hw:].unflatten(1, (rows - ns, nk)).permute(1, 0, 2), short
+
+    def _xf_cross_consume(self, st: _XfPass, text_cache: bool, shared: bool) -> torch.Tensor:
+        """Main pass: the text branch (q2 -> attn2, :266-276) and the image branch (q3 -> attn3, :281-290) write the two halves of one
+        [M, 2C] buffer; their out-projections, biases and both residual adds (:277,291-293) are one GEMM -> h3."""
+        xf, L, B, hw, C, heads, scale, S = st.xf, st.L, st.B, st.hw, st.C, st.heads, st.scale, self.S
+        kt3, vtt3 = self._text_kv(xf, st.lvl, text_cache)
+        att23, h1, h3 = L["att23"], L["h1"], L["h3"]
+        a2v, a3v = att23[:, :C].unflatten(0, (B, hw)), att23[:, C:].unflatten(0, (B, hw))
+        if shared:      # cfg_shared_head, first transformer: ONE query tensor for the three CFG samples
+            q2q = L["q2"][:hw].view(1, hw, C).expand(2, hw, C)
+            q3 = L["q"][:hw].view(1, hw, C).expand(2, hw, C)
+            kt3, vtt3, a2o, a3o = kt3[::2], vtt3[::2], a2v[::2], a3v[:2]       # text rows (uncond, text) -> samples 0 and 2
+        else:
+            q2q, q3, a2o, a3o = L["q2"].view(B, hw, C), L["q"].view(B, hw, C), a2v, a3v
+        # text + image attention as one launch when the image attention is one fp16 launch itself (else the text attention runs
+        # beside the context projections on the side stream)
+        paired = (ATTN_PAIR and self.attn3_share is not None and not self.ctx_short and not shared
+                  and not (self.fp8_attention and C == heads * 40))
+        forked = False if paired else self._fork()
+        if forked:
+            with torch.cuda.stream(self.side):
+                ops.attention(q2q, kt3, vtt3, a2o, heads, scale, nk=S)
+        elif not paired:
+            ops.attention(q2q, kt3, vtt3, a2o, heads, scale, nk=S)
+        ki3, vti3, short = self._ctx_kv(st)
+        if paired:
+            ops.attention_pair((q3, ki3, vti3, a3v, None), (q2q, kt3, vtt3, a2v, S), heads, scale)
+        elif self.attn3_share is not None:    # one launch: batch b reads context row b (b < rows) or b - (B - rows)
+            self._attention(q3, ki3, vti3, a3o, heads, scale, short=short)
+        else:
+            for q0, n, c0 in self.attn3_groups:
+                self._attention(q3[q0:q0 + n], ki3[c0:c0 + n], vti3[c0:c0 + n], a3v[q0:q0 + n], heads, scale)
+        if forked:
+            self._join()
+        if shared:      # sample 1 = (uncond text, frames): its text attention is sample 0's, its image attention sample 2 shares
+            ops.copy_rows(a2v[1:2], a2v[0:1])
+            ops.copy_rows(a3v[2:3], a3v[1:2])
+        ops.gemm(att23, xf.w_o23, h3, bias=xf.b_o23, res1=h1, res2=h1, workspace=self.ws_split, **st.prod3(h3))  # (a2 + h) + (a3 + h)
+        return h3
+
+    def _xf_cross_text(self, st: _XfPass, text_cache: bool) -> torch.Tensor:
+        """Reference pass: text cross-attention only (:266-277); h2 plays h3."""
+        xf, L, B, hw, C = st.xf, st.L, st.B, st.hw, st.C
+        kt3, vtt3 = self._text_kv(xf, st.lvl, text_cache)
+        ops.attention(L["q"].view(B, hw, C), kt3, vtt3, L["att"].view(B, hw, C), st.heads, st.scale, nk=self.S)
+        h3 = L["h2"]
+        ops.gemm(L["att"], xf.w_o2, h3, bias=xf.b_o2, res1=L["h1"], workspace=self.ws_split, **st.prod3(h3))   # :277,295
+        return h3
+
+    def _xf_feed_forward(self, st: _XfPass, h3: torch.Tensor):
+        """Feed-forward :298-300 and proj_out + the block's residual :121-123."""
+        xf, L, M, C, gd, ws, x, out = st.xf, st.L, st.M, st.C, st.guard, self.ws_split, st.x, st.out
         h4, w_out = L["h4"], xf.w_out
-        if ff1 and M <= FF_SPLIT_MAX_TOKENS:      # small launch: two workgroups per 128 tokens, partial sums side by side
+        if st.ff1 and M <= FF_SPLIT_MAX_TOKENS:      # small launch: two workgroups per 128 tokens, partial sums side by side
             # L["att23"] as scratch: its only reader, the w_o23 / w_o2 GEMM above, is behind us on this stream, and the next writer (the
             # cross-attentions of the next block at this level) comes after proj_out below has consumed the partial sums (advisor r5).
             # The two halves are rounded to fp16 separately and re-added by proj_out's K = 2C contraction: one more rounding than the
             # unsplit kernel's single fp16 output, covered by the full-depth parity tests on the default (split) schedule.
             h4, w_out = L["att23"], xf.w_out2
             ops.ff_fused(h3, xf.ff_pack, xf.b_ff2, h4, LN_EPS, split=True)
-        elif ff1:    # one launch: LayerNorm in registers, GEGLU intermediate never materialised (h4 is fp16: it only feeds proj_out)
+        elif st.ff1:    # one launch: LayerNorm in registers, GEGLU intermediate never materialised (h4 is fp16: it only feeds proj_out)
             ops.ff_fused(h3, xf.ff_pack, xf.b_ff2, L["h4"], LN_EPS)
-        elif merge:      # GEGLU into columns [0, 4C) of the buffer whose columns [4C, 5C) hold h3's raw copy; ff.net.2 happens inside proj_out's GEMM
-            ops.gemm(h3raw, xf.w_ff1f, L["ffo"][:M, :4 * C], epilogue=ops.EPI_GEGLU, ln=(1, L["lnst3"], xf.c_ff1, xf.d_ff1, LN_EPS), guard=gd)
+        elif st.merge:      # GEGLU into columns [0, 4C) of the buffer whose columns [4C, 5C) hold h3's raw copy; ff.net.2 happens inside proj_out's GEMM
+            ops.gemm(st.h3raw, xf.w_ff1f, L["ffo"][:M, :4 * C], epilogue=ops.EPI_GEGLU, ln=(1, L["lnst3"], xf.c_ff1, xf.d_ff1, LN_EPS), guard=gd)
             h4, w_out = L["ffo"][:M], xf.w_ffo
-        elif fold:
-            ops.gemm(raw(h3, L["ln"]), xf.w_ff1f, L["ffi"], epilogue=ops.EPI_GEGLU, ln=(1, L["lnst3"], xf.c_ff1, xf.d_ff1, LN_EPS), guard=gd)
+        elif st.fold:
+            ops.gemm(st.raw(h3, L["ln"]), xf.w_ff1f, L["ffi"], epilogue=ops.EPI_GEGLU, ln=(1, L["lnst3"], xf.c_ff1, xf.d_ff1, LN_EPS), guard=gd)
         else:
             ops.layernorm(h3, *xf.ln["norm3"], L["ln"])
             ops.gemm(L["ln"], xf.w_ff1, L["ffi"], bias=xf.b_ff1, epilogue=ops.EPI_GEGLU, workspace=ws)
-        if not ff1 and not merge:
+        if not st.ff1 and not st.merge:
             ops.gemm(L["ffi"], xf.w_ff2, L["h4"], bias=xf.b_ff2, res1=h3, workspace=ws)   # fp16: only feeds proj_out
-        kwo = dict(bias=xf.b_ffo if merge else xf.b_out, res1=x, workspace=ws)            # proj_out + residual :121-123
-        site = xf.spec.prefix + ".proj_out"
-        so = self._stats_for(site, lvl, C, lambda buf: ops.gemm_stats_rows(h4, w_out, out, stats=(buf, hw), **kwo))
-        ops.gemm(h4, w_out, out, stats=None if so is None else (so, hw), **kwo)
-        if so is not None:
-            self._publish(out, site, C)
-        else:
-            self._pstats.pop(out.data_ptr(), None)
+        kwo = dict(bias=xf.b_ffo if st.merge else xf.b_out, res1=x, workspace=ws)
+        self._produce(xf.spec.prefix + ".proj_out", st.lvl, C, out,
+                      lambda s: ops.gemm(h4, w_out, out, stats=None if s is None else (s, st.hw), **kwo),
+                      lambda buf: ops.gemm_stats_rows(h4, w_out, out, stats=(buf, st.hw), **kwo))
 
     def _sampler_conv(self, prefix: str, h: torch.Tensor, out: torch.Tensor, lvl: int, out_lvl: int, down: bool):
         """Downsample2D (3x3 stride 2) / Upsample2D (nearest 2x + 3x3): the fp32 stream tensor is cast into the
@@ -935,13 +932,8 @@ class UNetEngine:
         pbuf = self.padded[(lvl, h.shape[1])]
         ops.pad_cast(self._img(h, lvl), pbuf)
         kw = dict(stride=2 if down else 1, upsample2x=not down, bias=b, workspace=self.ws_split, x_padded=True)
-        n_out = out.shape[1]
-        st = self._stats_for(prefix, out_lvl, n_out, lambda buf: ops.conv3x3_stats_rows(pbuf, w, self._img(out, out_lvl), stats=buf, **kw))
-        ops.conv3x3(pbuf, w, self._img(out, out_lvl), stats=st, **kw)
-        if st is not None:
-            self._publish(out, prefix, n_out)
-        else:
-            self._pstats.pop(out.data_ptr(), None)
+        self._produce(prefix, out_lvl, out.shape[1], out, lambda s: ops.conv3x3(pbuf, w, self._img(out, out_lvl), stats=s, **kw),
+                      lambda buf: ops.conv3x3_stats_rows(pbuf, w, self._img(out, out_lvl), stats=buf, **kw))
 
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, harvest_slot: Optional[int] = None, consume: bool = False, harvest: Optional[HarvestPlan] = None,
@@ -1005,16 +997,14 @@ class UNetEngine:
             try:
                 sk0 = skips[0][: self.hw[0]]
                 self._resnet(r0, sk0, self.lv[0]["r"], 0, defer_out=True)
-                self._transformer(xf0, self.lv[0]["r"], None, 0, text, None, True, phase="front", **tk)
+                st = _XfPass(self, xf0, self.lv[0]["r"], None, 0, True)
+                self._xf_to_harvest(st, None)
+                self._xf_queries(st)
             finally:
                 self._leave_head(saved)
             for t2d in (self.lv[0]["r"], self.lv[0]["h1"]):                # proj_out's residual, the attentions' residual
                 self._spread(t2d, 1, 2)
-            self._shared_back = True
-            try:
-                self._transformer(xf0, self.lv[0]["r"], skips[1], 0, text, None, True, phase="back", **tk)
-            finally:
-                self._shared_back = False
+            self._xf_back(_XfPass(self, xf0, self.lv[0]["r"], skips[1], 0, True), text_cache, shared=True)
             h, lvl, si = skips[1], 0, 2
         else:
             # --- conv_in :411
@@ -1064,8 +1054,8 @@ class UNetEngine:
                     self._resnet(self.resnets[r.prefix], cat, out, lvl)
                 else:
                     self._resnet(self.resnets[r.prefix], cat, L["r"], lvl, defer_out=True)
-                    if xf.prefix == last_xf:
-                        self._transformer(self.xfs[xf.prefix], L["r"], None, lvl, text, harvest, consume, stop_after_harvest=True)
+                    if xf.prefix == last_xf:      # harvest_only: the pass ends with its last feature (before that block's text projections)
+                        self._xf_to_harvest(_XfPass(self, self.xfs[xf.prefix], L["r"], None, lvl, consume), harvest)
                         return None
                     self._transformer(self.xfs[xf.prefix], L["r"], out, lvl, text, harvest, consume, **tk)
                 k += 1
