@@ -449,6 +449,12 @@ int sg_pad_cast_f16(const void* x, int64_t ldx, int32_t x_f32, sg_half* y, int64
  * sg_attn_small_f16: O[b,i,h*D+:] = softmax_j(scale * Q[b,i,h,:].K[b,j,h,:] + key_bias[b,j] (+ causal mask j <= i)) V[b,j,h,:]
  *   for short sequences (T <= 128, D <= 64), heads interleaved in channels, V NOT transposed — CLIPAttention of the text
  *   encoder (transformers 4.27.4 modeling_clip.py; /root/reference/model/pipeline.py:137,183).  key_bias: fp32 [B, T] or NULL.
+ * sg_attn_enc_f16: the same contract for encoder-class sequences (CLIP ViT-H/14 of PickScore: 257 tokens, 16 heads of 80) on the
+ *   matrix cores: 1 <= T <= 1024, D a multiple of 8 in [8, 128], token strides >= H * D, every stride a multiple of 8 elements,
+ *   16-byte-aligned q/k/v/o.  Flash-style over tiles of 64 keys (fp32 online softmax, LDS use independent of T), V read token-major
+ *   (transposing LDS reads, no V^T buffer).  Keys >= T are never read.  A key bias of finfo(float32).min on every key of a tile
+ *   contributes exactly zero; on every key of a row it gives the uniform average.  Anything outside the range returns SG_EINVAL
+ *   before a launch.
  * sg_act_rows_f16: in place x = x*sigmoid(1.702x) (SG_ACT_QUICK_GELU, CLIPMLP "quick_gelu") or erf GELU (SG_ACT_GELU).
  * sg_embed_tokens_f32: out[r,:] = tok[ids[r],:] + pos[r % T,:] (CLIPTextEmbeddings), fp32 tables and output; ids are not
  *   range-checked on the device (the host validates them).
@@ -462,6 +468,9 @@ int sg_softmax_rows_f16(const float* s, int64_t lds, sg_half* p, int64_t ldp, in
 int sg_attn_small_f16(const sg_half* q, int64_t ldq, int64_t bsq, const sg_half* k, int64_t ldk, int64_t bsk, const sg_half* v,
                       int64_t ldv, int64_t bsv, sg_half* o, int64_t ldo, int64_t bso, const float* key_bias, int32_t B,
                       int32_t H, int32_t T, int32_t D, float scale, int32_t causal, sg_stream_t stream);
+int sg_attn_enc_f16(const sg_half* q, int64_t ldq, int64_t bsq, const sg_half* k, int64_t ldk, int64_t bsk, const sg_half* v,
+                    int64_t ldv, int64_t bsv, sg_half* o, int64_t ldo, int64_t bso, const float* key_bias, int32_t B,
+                    int32_t H, int32_t T, int32_t D, float scale, int32_t causal, sg_stream_t stream);
 int sg_act_rows_f16(sg_half* x, int64_t ldx, int32_t M, int32_t N, int32_t act, sg_stream_t stream);
 int sg_embed_tokens_f32(const int64_t* ids, const float* tok, const float* pos, float* out, int64_t ldo, int32_t rows, int32_t T,
                         int32_t C, sg_stream_t stream);
@@ -482,12 +491,17 @@ int sg_gaussian_sample_f32(const float* mean, const float* logvar, const float* 
  *   torch.nn.functional.interpolate(mode="bicubic", antialias=True, align_corners=False)) of the image at the pixel of the
  *   centre crop, in fp32.  mean and std are HOST arrays of 3 floats.  Returns SG_EINVAL without launching when S % ps != 0,
  *   3 * ps * ps is not a multiple of 8, a size is not positive, a pointer is null or a std is zero.
+ * sg_clip_patchify_padk_f16: the same rows, Kpad columns wide: columns [3 * ps * ps, Kpad) of every row are zeros, nothing beyond
+ *   Kpad is touched (patch size 14: 588 values padded to 592, the K of the patch GEMM against a weight with zero columns
+ *   appended).  Needs Kpad % 8 == 0, 3 * ps * ps <= Kpad <= ldo and 3 * ps * ps % 4 == 0; SG_EINVAL otherwise.
  * sg_clip_embed_patches_f32: CLIPVisionEmbeddings' concat and position add on the fp32 residual stream: out[b * T, :] =
  *   cls + pos[0], out[b * T + t, :] = patches[b * (T - 1) + t - 1, :] + pos[t] for 1 <= t < T.
  */
 int sg_clip_resize_geometry(int32_t H, int32_t W, int32_t S, int32_t* geom);
 int sg_clip_patchify_f16(const float* x, int32_t B, int32_t H, int32_t W, float in_scale, float in_shift, const float* mean,
                          const float* std, int32_t S, int32_t ps, sg_half* out, int64_t ldo, sg_stream_t stream);
+int sg_clip_patchify_padk_f16(const float* x, int32_t B, int32_t H, int32_t W, float in_scale, float in_shift, const float* mean,
+                              const float* std, int32_t S, int32_t ps, int32_t Kpad, sg_half* out, int64_t ldo, sg_stream_t stream);
 int sg_clip_embed_patches_f32(const float* patches, int64_t ldp, const float* cls, const float* pos, float* out, int64_t ldo,
                               int32_t B, int32_t T, int32_t C, sg_stream_t stream);
 

@@ -9,8 +9,8 @@ projected, L2-normalised features; the scripts print the mean over pairs).
 Weights are state dicts in transformers naming (CLIPVisionModelWithProjection / CLIPTextModelWithProjection, or one CLIPModel state
 dict passed for both); the tokenizer is the caller's.  Images go through sg_clip_patchify_f16 — the `clip` package's resize (antialiased
 bicubic on the float image), centre crop and normalisation — and ClipVisionEngine; texts through ClipTextEngine and its projection.
-Models outside sg_attn_small_f16 (more than 128 tokens, head dim above 64: ViT-H/14, PickScore) are refused on the host.  There is no
-CPU path."""
+Models outside sg_attn_small_f16 (more than 128 tokens, head dim above 64: ViT-H/14) are refused on the host; PickScore's ViT-H/14 runs in
+storygen_amd/pick_score.py.  There is no CPU path."""
 from __future__ import annotations
 
 from typing import Dict, Optional

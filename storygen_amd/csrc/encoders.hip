@@ -8,6 +8,7 @@
 //   gaussian_sample_kernel  DiagonalGaussianDistribution.sample() * scaling factor
 // and the front of the CLIP image tower (CLIP-I / CLIP-T scoring of generated frames):
 //   clip_patchify_kernel       antialiased bicubic resize + centre crop + normalise + patch gather, float image -> fp16 GEMM rows
+//                              (optionally zero-padded to a K that is a multiple of 8: patch size 14, sg_clip_patchify_padk_f16)
 //   clip_embed_patches_kernel  class token + patch rows + position embedding into the fp32 residual stream
 #include "common.h"
 
@@ -196,9 +197,10 @@ __device__ __forceinline__ float patchify_value(const float* x, const PatchifyAr
 
 // One thread per 8 consecutive columns of one output row (one 16-byte store).  Row = b * P + patch (row-major patches), column =
 // (c * ps + dy) * ps + dx: the layout of patch_embedding.weight.view(C, 3 * ps * ps).  The separable weights are evaluated per output
-// value (<= 11 x 11 taps at 512 -> 224): no intermediate image, fp32 throughout.
-__global__ __launch_bounds__(256) void clip_patchify_kernel(const float* x, f16* out, long ldo, PatchifyArgs a) {
-    const int K = 3 * a.ps * a.ps, vpr = K / 8, G = a.S / a.ps, P = G * G;
+// value (<= 11 x 11 taps at 512 -> 224): no intermediate image, fp32 throughout.  Columns [3 * ps * ps, Kpad) are written as zeros (the patch GEMM's
+// K dimension when 3 * ps * ps is no multiple of 8: patch size 14); sg_clip_patchify_f16 passes Kpad = 3 * ps * ps.
+__global__ __launch_bounds__(256) void clip_patchify_kernel(const float* x, f16* out, long ldo, PatchifyArgs a, int Kpad) {
+    const int K = 3 * a.ps * a.ps, vpr = Kpad / 8, G = a.S / a.ps, P = G * G;
     const long total = (long)a.B * P * vpr;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const long row = idx / vpr;
@@ -207,7 +209,7 @@ __global__ __launch_bounds__(256) void clip_patchify_kernel(const float* x, f16*
         const int py = p / G, px = p - py * G;
         float o[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = patchify_value(x, a, b, py, px, col0 + e);
+        for (int e = 0; e < 8; ++e) o[e] = col0 + e < K ? patchify_value(x, a, b, py, px, col0 + e) : 0.f;
         store8h(out + row * ldo + col0, o);
     }
 }
@@ -307,6 +309,23 @@ extern "C" int sg_clip_resize_geometry(int32_t H, int32_t W, int32_t S, int32_t*
     return SG_OK;
 }
 
+// The shared tail of the two patchify entry points: geometry, arguments, launch.  Kpad = row width written (>= 3 * ps * ps, multiple of 8).
+static int clip_patchify_launch(const char* who, const float* x, int32_t B, int32_t H, int32_t W, float in_scale, float in_shift, const float* mean,
+                                const float* std, int32_t S, int32_t ps, int32_t Kpad, sg_half* out, int64_t ldo, sg_stream_t stream) {
+    int32_t g[4];
+    if (int e = sg_clip_resize_geometry(H, W, S, g)) return e;
+    PatchifyArgs a;
+    a.B = B, a.H = H, a.W = W, a.S = S, a.ps = ps, a.RH = g[0], a.RW = g[1], a.top = g[2], a.left = g[3];
+    a.sy = (float)H / (float)a.RH, a.sx = (float)W / (float)a.RW;
+    a.in_scale = in_scale, a.in_shift = in_shift;
+    for (int c = 0; c < 3; ++c) a.mean[c] = mean[c], a.std[c] = std[c];
+    const long total = (long)B * (S / ps) * (S / ps) * (Kpad / 8);
+    const int blocks = (int)(total / 256 + 1 < 65536 ? total / 256 + 1 : 65536);
+    hipLaunchKernelGGL(clip_patchify_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<f16*>(out), (long)ldo, a, Kpad);
+    SG_CHECK_LAUNCH(who);
+    return SG_OK;
+}
+
 extern "C" int sg_clip_patchify_f16(const float* x, int32_t B, int32_t H, int32_t W, float in_scale, float in_shift, const float* mean,
                                     const float* std, int32_t S, int32_t ps, sg_half* out, int64_t ldo, sg_stream_t stream) {
     SG_REQUIRE(x && mean && std && out, "sg_clip_patchify: null pointer");
@@ -316,18 +335,22 @@ extern "C" int sg_clip_patchify_f16(const float* x, int32_t B, int32_t H, int32_
     SG_REQUIRE((3 * ps * ps) % 8 == 0, "sg_clip_patchify: 3 * ps * ps (%d) must be a multiple of 8", 3 * ps * ps);
     SG_REQUIRE(ldo % 8 == 0 && ldo >= 3 * ps * ps && sg_aligned16(out), "sg_clip_patchify: output row stride / alignment");
     SG_REQUIRE(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "sg_clip_patchify: zero std");
-    int32_t g[4];
-    if (int e = sg_clip_resize_geometry(H, W, S, g)) return e;
-    PatchifyArgs a;
-    a.B = B, a.H = H, a.W = W, a.S = S, a.ps = ps, a.RH = g[0], a.RW = g[1], a.top = g[2], a.left = g[3];
-    a.sy = (float)H / (float)a.RH, a.sx = (float)W / (float)a.RW;
-    a.in_scale = in_scale, a.in_shift = in_shift;
-    for (int c = 0; c < 3; ++c) a.mean[c] = mean[c], a.std[c] = std[c];
-    const long total = (long)B * (S / ps) * (S / ps) * (3 * ps * ps / 8);
-    const int blocks = (int)(total / 256 + 1 < 65536 ? total / 256 + 1 : 65536);
-    hipLaunchKernelGGL(clip_patchify_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<f16*>(out), (long)ldo, a);
-    SG_CHECK_LAUNCH("sg_clip_patchify_f16");
-    return SG_OK;
+    return clip_patchify_launch("sg_clip_patchify_f16", x, B, H, W, in_scale, in_shift, mean, std, S, ps, 3 * ps * ps, out, ldo, stream);
+}
+
+extern "C" int sg_clip_patchify_padk_f16(const float* x, int32_t B, int32_t H, int32_t W, float in_scale, float in_shift, const float* mean,
+                                         const float* std, int32_t S, int32_t ps, int32_t Kpad, sg_half* out, int64_t ldo, sg_stream_t stream) {
+    SG_REQUIRE(x && mean && std && out, "sg_clip_patchify_padk: null pointer");
+    SG_REQUIRE(B > 0 && H > 0 && W > 0 && S > 0 && ps > 0 && ps <= 256 && H <= (1 << 15) && W <= (1 << 15) && S <= (1 << 15),
+               "sg_clip_patchify_padk: bad size B=%d H=%d W=%d S=%d ps=%d", B, H, W, S, ps);
+    SG_REQUIRE(S % ps == 0, "sg_clip_patchify_padk: the crop size %d is not a multiple of the patch size %d", S, ps);
+    SG_REQUIRE((3 * ps * ps) % 4 == 0, "sg_clip_patchify_padk: 3 * ps * ps (%d) must be a multiple of 4", 3 * ps * ps);
+    SG_REQUIRE(Kpad % 8 == 0 && Kpad >= 3 * ps * ps, "sg_clip_patchify_padk: Kpad (%d) must be a multiple of 8 and at least 3 * ps * ps (%d)", Kpad,
+               3 * ps * ps);
+    SG_REQUIRE(ldo % 8 == 0 && ldo >= Kpad && sg_aligned16(out), "sg_clip_patchify_padk: output row stride %lld below Kpad %d / alignment",
+               (long long)ldo, Kpad);
+    SG_REQUIRE(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "sg_clip_patchify_padk: zero std");
+    return clip_patchify_launch("sg_clip_patchify_padk_f16", x, B, H, W, in_scale, in_shift, mean, std, S, ps, Kpad, out, ldo, stream);
 }
 
 extern "C" int sg_clip_embed_patches_f32(const float* patches, int64_t ldp, const float* cls, const float* pos, float* out, int64_t ldo,

@@ -48,6 +48,17 @@ def check_clip_dims(who: str, hidden: int, heads: int, tokens: int) -> None:
         raise ValueError(f"{who}: {tokens} tokens exceed sg_attn_small_f16's 128 (ViT-H/14, 257 tokens of head dim 80, is out of scope)")
 
 
+def check_clip_dims_wide(who: str, hidden: int, heads: int, tokens: int) -> None:
+    """The limits of sg_attn_enc_f16 / sg_gemm_f16 for a CLIP tower (ClipVisionEngine(wide=True): ViT-H/14, PickScore)."""
+    if heads <= 0 or hidden % heads or hidden % 8:
+        raise ValueError(f"{who}: hidden size {hidden} does not split into {heads} heads of whole 8-channel groups")
+    d = hidden // heads
+    if d % 8 or d < 8 or d > 128:
+        raise ValueError(f"{who}: head dim {d} is outside sg_attn_enc_f16 (a multiple of 8 in [8, 128])")
+    if tokens < 1 or tokens > 1024:
+        raise ValueError(f"{who}: {tokens} tokens exceed sg_attn_enc_f16's 1024")
+
+
 class _ClipLayers:
     """The pre-LN transformer layers both CLIP towers share (transformers CLIPEncoder): weights of `encoder.layers.*` and the launch
     sequence of one pass over them.  The residual stream is fp32, every MFMA operand fp16."""
@@ -88,10 +99,12 @@ class _ClipLayers:
         u16 = torch.empty(M, self.inner, dtype=F16, device=dev)
         q3 = qkv.view(B, T, 3 * C)
         scale = (C // H) ** -0.5
+        # per tower: the scalar LDS-resident kernel where it fits (CLIP text, ViT-B/32), the MFMA encoder kernel beyond it (ViT-H/14)
+        attn = ops.attention_small if T <= 128 and C // H <= 64 else ops.attention_enc
         for L in self.layers:
             ops.layernorm(x, L["ln1"][0], L["ln1"][1], h16, self.eps)
             ops.gemm(h16, L["wqkv"], qkv, bias=L["bqkv"], workspace=self.ws)
-            ops.attention_small(q3[:, :, :C], q3[:, :, C:2 * C], q3[:, :, 2 * C:], a16.view(B, T, C), H, scale, causal, key_bias)
+            attn(q3[:, :, :C], q3[:, :, C:2 * C], q3[:, :, 2 * C:], a16.view(B, T, C), H, scale, causal, key_bias)
             ops.gemm(a16, L["wo"], x2, bias=L["bo"], res1=x, workspace=self.ws)
             ops.layernorm(x2, L["ln2"][0], L["ln2"][1], h16, self.eps)
             ops.gemm(h16, L["w1"], u16, bias=L["b1"], workspace=self.ws)
@@ -162,10 +175,12 @@ class ClipTextEngine:
 
 class ClipVisionEngine:
     """CLIP image tower with its projection head — transformers CLIPVisionTransformer + visual_projection (ViT-B/32 class: at most 128
-    tokens, head dim <= 64), fed by sg_clip_patchify_f16: float images of any size in, (image_embeds, last_hidden_state) out."""
+    tokens, head dim <= 64), fed by sg_clip_patchify_f16: float images of any size in, (image_embeds, last_hidden_state) out.
+    wide=True lifts the limits to sg_attn_enc_f16's (up to 1024 tokens, head dim a multiple of 8 up to 128: ViT-H/14, PickScore) and
+    rounds the patch row 3 * ps^2 up to a multiple of 8 (patch size 14: 588 -> 592, zero columns appended once to the fp16 patch weight)."""
 
     def __init__(self, state_dict: SD, device, heads: int = 12, eps: float = 1e-5, hidden_act: str = "quick_gelu",
-                 image_size: Optional[int] = None):
+                 image_size: Optional[int] = None, wide: bool = False):
         sd = {k[len("vision_model."):] if k.startswith("vision_model.") else k: v for k, v in state_dict.items()}
         wp = sd["embeddings.patch_embedding.weight"]                       # [C, 3, ps, ps]
         pos = sd["embeddings.position_embedding.weight"]                   # [T, C]
@@ -176,9 +191,17 @@ class ClipVisionEngine:
         self.S = grid * self.ps
         if image_size is not None and image_size != self.S:
             raise ValueError(f"ClipVisionEngine: image_size {image_size} does not match {grid} x {grid} patches of {self.ps}")
-        check_clip_dims("ClipVisionEngine", self.C, heads, self.T)
-        if (3 * self.ps * self.ps) % 8:
-            raise ValueError(f"ClipVisionEngine: 3 * patch_size^2 = {3 * self.ps * self.ps} must be a multiple of 8")
+        K = 3 * self.ps * self.ps
+        self.wide, self.kpad = bool(wide), K
+        if wide:
+            check_clip_dims_wide("ClipVisionEngine", self.C, heads, self.T)
+            if K % 4:
+                raise ValueError(f"ClipVisionEngine: 3 * patch_size^2 = {K} must be a multiple of 4")
+            self.kpad = (K + 7) & ~7
+        else:
+            check_clip_dims("ClipVisionEngine", self.C, heads, self.T)
+            if K % 8:
+                raise ValueError(f"ClipVisionEngine: 3 * patch_size^2 = {K} must be a multiple of 8")
         self.pdim = sd["visual_projection.weight"].shape[0]
         if self.pdim % 8:
             raise ValueError(f"ClipVisionEngine: projection_dim {self.pdim} must be a multiple of 8")
@@ -188,7 +211,9 @@ class ClipVisionEngine:
         def d16(t):
             return t.detach().to(self.dev, F32).to(F16).contiguous()
 
-        self.wp = d16(wp.reshape(self.C, 3 * self.ps * self.ps))           # (c, dy, dx) columns: the patchify kernel's order
+        self.wp = d16(wp.reshape(self.C, K))                               # (c, dy, dx) columns: the patchify kernel's order
+        if self.kpad != K:                                                 # zero columns against the zero columns of the padded patch rows
+            self.wp = torch.nn.functional.pad(self.wp, (0, self.kpad - K)).contiguous()
         self.cls = sd["embeddings.class_embedding"].detach().to(self.dev, F32).contiguous()
         self.pos = pos.detach().to(self.dev, F32).contiguous()
         self.pre = (d16(sd["pre_layrnorm.weight"]), d16(sd["pre_layrnorm.bias"]))
@@ -206,8 +231,11 @@ class ClipVisionEngine:
         dev, C, T, K = self.dev, self.C, self.T, 3 * self.ps * self.ps
         B = images.shape[0]
         img = images.detach().to(dev, F32).contiguous()
-        a16 = torch.empty(B * (T - 1), K, dtype=F16, device=dev)
-        ops.clip_patchify(img, a16, self.S, self.ps, mean, std, in_scale, in_shift)
+        a16 = torch.empty(B * (T - 1), self.kpad, dtype=F16, device=dev)
+        if self.kpad == K:
+            ops.clip_patchify(img, a16, self.S, self.ps, mean, std, in_scale, in_shift)
+        else:
+            ops.clip_patchify(img, a16, self.S, self.ps, mean, std, in_scale, in_shift, kpad=self.kpad)
         pe = torch.empty(B * (T - 1), C, dtype=F32, device=dev)
         ops.gemm(a16, self.wp, pe, workspace=self.ws)
         e = torch.empty(B * T, C, dtype=F32, device=dev)

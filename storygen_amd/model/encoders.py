@@ -1,4 +1,4 @@
-"""Drop-in `AutoencoderKL`, `CLIPTextModel` and `CLIPVisionModelWithProjection` on the HIP engines of storygen_amd/encoders.py.
+"""Drop-in `AutoencoderKL`, `CLIPTextModel`, `CLIPVisionModelWithProjection` and `CLIPModel` on the HIP engines of storygen_amd/encoders.py.
 
 They mirror what the reference's scripts and pipeline touch, nothing more:
 
@@ -10,6 +10,9 @@ They mirror what the reference's scripts and pipeline touch, nothing more:
   text_encoder.config.use_attention_mask                           model/pipeline.py:128-135
   CLIPVisionModelWithProjection(pixel_values).image_embeds          the image tower of the evaluation's CLIP-I / CLIP-T scores
                                                                     (ViT-B/32 class; storygen_amd/clip_score.py feeds it raw frames)
+  AutoModel.from_pretrained("yuvalkirstain/PickScore_v1")           evaluation/calc_Pickscore.py:32, inference_COCO_val.py:30 -> CLIPModel
+  model.get_image_features(pixel_values=...), .get_text_features(input_ids=..., attention_mask=...), model.logit_scale.exp()
+                                                                    calc_Pickscore.py:16-21, inference_COCO_val.py:30-36 (CLIP ViT-H/14)
 
 Weights keep the third-party packages' names and layouts (diffusers 0.13.1 AutoencoderKL, transformers CLIPTextModel), so their
 checkpoints load unchanged; `from_torch(module)` adopts an already-constructed torch module of either package.  Inference only (the
@@ -436,3 +439,89 @@ class CLIPVisionModelWithProjection(_HipModule):
         return CLIPVisionModelOutput(embeds.to(self.dtype), hidden.to(self.dtype))
 
     __call__ = forward
+
+
+# ------------------------------------------------------------------------------------------------- CLIP, both towers (PickScore)
+CLIP_MODEL_DEFAULTS = OrderedDict(projection_dim=512, logit_scale_init_value=2.6592, initializer_factor=1.0, model_type="clip")
+
+
+class CLIPModel(_HipModule):
+    """transformers' CLIPModel as the reference's PickScore code uses it (calc_probs of evaluation/calc_Pickscore.py and
+    inference_COCO_val.py): get_image_features, get_text_features and logit_scale.  The image tower is ClipVisionEngine(wide=True)
+    (sg_attn_enc_f16: ViT-H/14's 257 tokens of head dim 80), the text tower ClipTextEngine; both live inside one PickScorer."""
+
+    def __init__(self, config: Optional[dict] = None, seed: int = 0, **kwargs):
+        from ..pick_score import check_pick_config
+        raw = config.to_dict() if hasattr(config, "to_dict") else dict(config or {})
+        raw.update(kwargs)
+        if not isinstance(raw.get("vision_config"), dict) or not isinstance(raw.get("text_config"), dict):
+            raise KeyError("CLIPModel: config needs vision_config and text_config dicts")
+        cfg = OrderedDict(CLIP_MODEL_DEFAULTS)
+        cfg.update({k: v for k, v in raw.items() if k in CLIP_MODEL_DEFAULTS})
+        vc, tc = OrderedDict(CLIP_VISION_DEFAULTS), OrderedDict(CLIP_TEXT_DEFAULTS)
+        vc.update({k: v for k, v in raw["vision_config"].items() if k in CLIP_VISION_DEFAULTS})
+        tc.update({k: v for k, v in raw["text_config"].items() if k in CLIP_TEXT_DEFAULTS})
+        vc["projection_dim"] = tc["projection_dim"] = cfg["projection_dim"]
+        if vc.get("num_channels", 3) != 3 or cfg["projection_dim"] % 8:
+            raise ValueError("CLIPModel: num_channels must be 3 and projection_dim a multiple of 8")
+        check_pick_config(vc, tc, "CLIPModel")
+        cfg["vision_config"], cfg["text_config"] = dict(vc), dict(tc)
+        self._config = FrozenConfig(cfg).freeze()
+        self._shapes = clip_vision_param_shapes(vc["hidden_size"], vc["intermediate_size"], vc["num_hidden_layers"], vc["image_size"],
+                                                vc["patch_size"], cfg["projection_dim"])
+        self._shapes.update(clip_text_param_shapes(tc["vocab_size"], tc["hidden_size"], tc["intermediate_size"], tc["num_hidden_layers"],
+                                                   tc["max_position_embeddings"]))
+        self._shapes["text_projection.weight"] = (cfg["projection_dim"], tc["hidden_size"])
+        self._sd: SD = init_state(self._shapes, seed, embed_std=vc["initializer_range"])
+        self._shapes["logit_scale"] = ()
+        self._sd["logit_scale"] = torch.tensor(float(cfg["logit_scale_init_value"]))
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_path: str, subfolder: Optional[str] = None, torch_dtype: Optional[torch.dtype] = None,
+                        **kwargs) -> "CLIPModel":
+        folder = os.path.join(pretrained_model_path, subfolder or "")
+        with open(os.path.join(folder, CONFIG_NAME)) as f:
+            model = cls(json.load(f))
+        model.load_state_dict(_load_weights(folder, CLIP_WEIGHTS), strict=False)
+        return model.to(torch_dtype) if torch_dtype is not None else model
+
+    @classmethod
+    def from_torch(cls, module) -> "CLIPModel":
+        """Adopt a constructed transformers CLIPModel."""
+        model = cls(module.config.to_dict() if hasattr(module.config, "to_dict") else dict(module.config))
+        model.load_state_dict(module.state_dict(), strict=False)
+        p = next(iter(module.state_dict().values()))
+        return model.to(p.device, p.dtype)
+
+    def load_state_dict(self, state_dict: SD, strict: bool = True):
+        """transformers CLIPModel names; the non-parameter `position_ids` buffers of old checkpoints are ignored."""
+        sd = {k: v for k, v in state_dict.items() if not k.endswith("position_ids")}
+        missing = [k for k in self._shapes if k not in sd]
+        if missing:
+            raise RuntimeError(f"CLIPModel.load_state_dict: missing {missing[:4]} (+{max(0, len(missing) - 4)} more)")
+        self._adopt(sd, self._shapes, strict)
+
+    def save_pretrained(self, save_directory: str, safe_serialization: bool = False, **kwargs):
+        self._save(save_directory, "CLIPModel", CLIP_WEIGHTS[1], CLIP_WEIGHTS[0], safe_serialization, {"architectures": ["CLIPModel"]})
+
+    @property
+    def logit_scale(self) -> torch.Tensor:
+        return self._sd["logit_scale"]
+
+    def _eng(self):
+        if self._engine is None:
+            from ..pick_score import PickScorer
+            if self.device.type != "cuda":
+                raise RuntimeError("CLIPModel: move the model to the HIP device first (.to('cuda')); there is no CPU path")
+            self._engine = PickScorer(self._sd, self._config, self.device)
+        return self._engine
+
+    def get_image_features(self, pixel_values: torch.Tensor, **kwargs) -> torch.Tensor:
+        """pixel_values [B, 3, image_size, image_size], already resized and normalised -> projected embeddings [B, projection_dim]."""
+        S = self._config["vision_config"]["image_size"]
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, S, S):
+            raise ValueError(f"CLIPModel: pixel_values must be [B,3,{S},{S}], got {tuple(pixel_values.shape)}")
+        return self._eng().pixel_features(pixel_values).to(self.dtype)
+
+    def get_text_features(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        return self._eng().text_features(input_ids, attention_mask).to(self.dtype)

@@ -620,6 +620,27 @@ def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torc
     return out
 
 
+def attention_enc(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int, scale: float, causal: bool,
+                  key_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Encoder-class attention on the matrix cores (1 <= T <= 1024, head dim a multiple of 8 up to 128: CLIP ViT-H/14), the contract of
+    attention_small: q/k/v/out [B,T,H*D] token-/batch-strided fp16 views, V not transposed; key_bias = optional fp32 [B,T] additive term."""
+    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _f16(t, n)
+        if t.dim() != 3 or t.stride(-1) != 1 or t.shape != q.shape:
+            raise ValueError(f"attention_enc: {n} must be [B,T,H*D] with a contiguous last dimension")
+    B, T, Cq = q.shape
+    if heads <= 0 or Cq % heads:
+        raise ValueError(f"attention_enc: {Cq} channels do not split into {heads} heads")
+    if key_bias is not None:
+        _f32(key_bias, "key_bias")
+        if tuple(key_bias.shape) != (B, T) or not key_bias.is_contiguous():
+            raise ValueError("attention_enc: key_bias must be a contiguous [B,T] tensor")
+    check(lib.sg_attn_enc_f16(q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), v.data_ptr(), v.stride(1),
+                              v.stride(0), out.data_ptr(), out.stride(1), out.stride(0), _p(key_bias), B, heads, T, Cq // heads,
+                              float(scale), int(causal), _stream()), "sg_attn_enc_f16")
+    return out
+
+
 ACT_QUICK_GELU, ACT_GELU = 0, 1
 
 
@@ -662,9 +683,12 @@ def clip_resize_geometry(H: int, W: int, S: int) -> tuple:
     return tuple(g)
 
 
-def clip_patchify(x: torch.Tensor, out: torch.Tensor, S: int, ps: int, mean, std, in_scale: float = 1.0, in_shift: float = 0.0) -> torch.Tensor:
+def clip_patchify(x: torch.Tensor, out: torch.Tensor, S: int, ps: int, mean, std, in_scale: float = 1.0, in_shift: float = 0.0,
+                  kpad: Optional[int] = None) -> torch.Tensor:
     """x fp32 NCHW [B,3,H,W] -> out fp16 [B * (S/ps)^2, 3*ps*ps]: (in_scale * x + in_shift) resized (antialiased bicubic) so that the shorter
-    side is S, centre-cropped to S x S, normalised with the per-channel mean / std (3 floats each) and cut into patches, columns (c, dy, dx)."""
+    side is S, centre-cropped to S x S, normalised with the per-channel mean / std (3 floats each) and cut into patches, columns (c, dy, dx).
+    kpad (a multiple of 8, >= 3*ps*ps): out is [rows, >= kpad] and columns [3*ps*ps, kpad) are written as zeros (sg_clip_patchify_padk_f16:
+    patch size 14); columns beyond kpad are left alone."""
     _f32(x, "x"), _f16(out, "out")
     if x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
         raise ValueError(f"clip_patchify: x must be a contiguous [B,3,H,W] tensor, got {tuple(x.shape)}")
@@ -673,9 +697,15 @@ def clip_patchify(x: torch.Tensor, out: torch.Tensor, S: int, ps: int, mean, std
     B, _, H, W = x.shape
     if S <= 0 or ps <= 0 or S % ps:
         raise ValueError(f"clip_patchify: crop size {S} is not a multiple of patch size {ps}")
+    m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    if kpad is not None:
+        if out.dim() != 2 or out.shape[0] != B * (S // ps) ** 2 or out.shape[1] < kpad:
+            raise ValueError(f"clip_patchify: out must be [{B * (S // ps) ** 2}, >= {kpad}], got {tuple(out.shape)}")
+        check(lib.sg_clip_patchify_padk_f16(x.data_ptr(), B, H, W, float(in_scale), float(in_shift), m, s, int(S), int(ps), int(kpad),
+                                            out.data_ptr(), _row_stride(out, "out"), _stream()), "sg_clip_patchify_padk_f16")
+        return out
     if out.dim() != 2 or tuple(out.shape) != (B * (S // ps) ** 2, 3 * ps * ps):
         raise ValueError(f"clip_patchify: out must be [{B * (S // ps) ** 2},{3 * ps * ps}], got {tuple(out.shape)}")
-    m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
     check(lib.sg_clip_patchify_f16(x.data_ptr(), B, H, W, float(in_scale), float(in_shift), m, s, int(S), int(ps), out.data_ptr(),
                                    _row_stride(out, "out"), _stream()), "sg_clip_patchify_f16")
     return out
