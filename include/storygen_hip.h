@@ -672,7 +672,8 @@ int sg_debug_ff_anatomy(const sg_ff_desc* d, void* prof, size_t prof_bytes, sg_s
  * library never reads the environment (storygen_amd/ops.py maps the SG_* variables of its tools onto this call).  name / value:
  *   "tile_m", "tile_n"   force a GEMM / conv tile (same effect as sg_debug_set_tile)      "no_pipe", "no_split"  1 = disable
  *   "no_nmajor"          1 = M-major tile order everywhere
- *   "attn_sub2", "attn_prio", "attn_d80" (0..2), "attn_d160" (0..4; 4 = key-split workgroups at Nq <= 256, default)  attention instantiation selectors
+ *   "attn_d160"          D = 160 attention: 4 = key-split workgroups at Nq <= 256 (default), 3 = always the query-split kernel;
+ *                        any other value is refused with SG_EINVAL
  *   "attn_d40_loop"      1 = D = 40 attention on the shared tile loop (the body before the tile-0 / steady-state / drain split; bit-identical)
  *   "gn_no_fused", "gn_wide", "gn_fused_max"                                            GroupNorm kernel selection
  *   "lat_tiles" (640; 0 = only on a tile hint), "lat_min_kt" (8), "lat_max_kt" (64), "lat_stages" (4 | 8), "lat_wide" (0 | 1: M <= "lat_wide_m"

@@ -82,49 +82,30 @@ static int attn_fwd(const sg_attn_desc* d, float* lse2, sg_stream_t stream) {
         // scale * log2(e) * Q to fp16 and keeps the maximum as two fp16 values, which costs lse2 ~|lse2| * 2^-12: 4e-4 .. 8e-4 on N(0, 1)
         // inputs and 1.3e-2 at a common logit offset of ~70 (tests/test_attention_backward_edges_gpu.py, bar 2e-3; the other head
         // dims: 1e-6).  The backward recomputes every P from lse2, so the training forward pays the ~66 VALU instructions per tile.
-        if (d->D == 40) launch_attn<40, 4, 3, 1, false, true, false, true>(p, st);
-        else if (d->D == 80) launch_attn<80, 4, 3, 1, false, true>(p, st);
-        else launch_attn<160, 4, 3, 1, false, true>(p, st);
+        if (d->D == 40) launch_attn<40, 4, 3, true, false, true>(p, st);
+        else if (d->D == 80) launch_attn<80, 4, 3, true>(p, st);
+        else launch_attn<160, 4, 3, true>(p, st);
         SG_CHECK_LAUNCH("sg_attn_fwd_lse_f16");
         return SG_OK;
     }
     const bool big = attn_big(d);
     const SgOptions& opt = sg_options();          // development options (sg_debug_set_option), defaults in common.h
-    const int sub2 = opt.attn_sub2, prio = opt.attn_prio;
+    // Every head dim runs 4 waves on a 3-deep ring where the grid allows it (measured against 2 waves and 2 stages at D = 80 / 160: HISTORY.md §5.1).
     if (d->D == 40) {
-        if (big && sub2 && d->Nk >= 256) launch_attn<40, 4, 2, 2>(p, st);   // 128 keys per barrier, 2-stage ring
-        else if (big && prio) launch_attn<40, 4, 3, 1, true>(p, st);
-        else if (big && opt.attn_d40_general) launch_attn<40, 4, 3, 1, false, false, false, true>(p, st);   // round-3 softmax (A/B)
-        else if (big && opt.attn_lean) launch_attn<40, 4, 3, 1, false, false, true>(p, st);   // V^T fragments per k-step: fewer VGPRs
+        if (big && opt.attn_d40_general) launch_attn<40, 4, 3, false, false, true>(p, st);   // round-3 softmax (A/B)
+        else if (big && opt.attn_lean) launch_attn<40, 4, 3, false, true>(p, st);   // V^T fragments per k-step: fewer VGPRs
         // round 7: tile 0 / branch-free steady state / drain (attn_d40_body, bit-identical); option attn_d40_loop = 1: the shared body
         else if (opt.attn_d40_loop == 1) big ? launch_attn<40, 4, 3>(p, st) : launch_attn<40, 2, 2>(p, st);
         else if (big) launch_attn_d40<4, 3>(p, st);
         else launch_attn_d40<2, 2>(p, st);
     }
-    else if (d->D == 80) {
-        // measured (tools/bench_norm.py --attn, B3 Nq1024 Nk3072): 2 waves x 2 stages 76.6 us, 2 x 3 59.8, 4 x 3 55.2 — the
-        // deeper ring matters more than the number of workgroups here.  option attn_d80 (sg_debug_set_option): 1 = always 4 x 3
-        // (default), 0 = 4 x 3 only when the grid fills the chip else 2 x 2, 2 = always 2 x 3
-        const int v80 = opt.attn_d80;
-        if (v80 == 1 || (v80 == 0 && big)) launch_attn<80, 4, 3>(p, st);
-        else if (v80 == 2) launch_attn<80, 2, 3>(p, st);
-        else launch_attn<80, 2, 2>(p, st);
-    }
-    else {
-        // the 16x16 level has few workgroups with long key loops; measured (tools/bench_norm.py --attn, B3 Nq256 Nk768):
-        // 2 waves x 2 stages 30.3 us, 2 x 3 30.2, 4 x 2 25.6, 4 x 3 25.4 -> 4 waves x 3 stages.  option attn_d160 = 0..3 picks
-        // one of the four (development knob).
-        // round 5: at Nq <= 256 (the 16x16 / 8x8 levels) the four waves of a workgroup split the KEYS of one 32-query block instead of
-        // taking 32 queries each (attn_fwd_ksplit_kernel) — option attn_d160 = 4 (default); 0..3 = the query-split instantiations
-        const int v160 = opt.attn_d160;
-        // (only where it wins, tools/calls/r5_call09.sh: one round of workgroups — a 160 KB workgroup owns its CU — and at least two
-        // tiles of keys; batch 20 of the batched reference pass, 1 280 workgroups, measured 42.7 vs 27.4 us)
-        if (v160 == 4 && d->Nq <= 256 && d->Nk > KVBLK && (long)sg_cdiv(d->Nq, 32) * d->H * d->B <= 256) launch_attn_ksplit<160, 4>(p, st);
-        else if (v160 == 1) launch_attn<160, 2, 3>(p, st);
-        else if (v160 == 2) launch_attn<160, 4, 2>(p, st);
-        else if (v160 == 3 || v160 == 4) launch_attn<160, 4, 3>(p, st);
-        else launch_attn<160, 2, 2>(p, st);
-    }
+    else if (d->D == 80) launch_attn<80, 4, 3>(p, st);
+    // D = 160, round 5: at Nq <= 256 (the 16x16 / 8x8 levels) the four waves of a workgroup split the KEYS of one 32-query block instead
+    // of taking 32 queries each (attn_fwd_ksplit_kernel) — only where it wins: one round of workgroups (a 160 KB workgroup owns its CU)
+    // and at least two tiles of keys; batch 20 of the batched reference pass, 1 280 workgroups, measured 42.7 vs 27.4 us.
+    // option attn_d160 = 4 (default); 3 = always the query-split kernel (what the parity tests compare against)
+    else if (opt.attn_d160 == 4 && d->Nq <= 256 && d->Nk > KVBLK && (long)sg_cdiv(d->Nq, 32) * d->H * d->B <= 256) launch_attn_ksplit<160, 4>(p, st);
+    else launch_attn<160, 4, 3>(p, st);
     SG_CHECK_LAUNCH("sg_attn_fwd_f16");
     return SG_OK;
 }
@@ -140,8 +121,7 @@ extern "C" int sg_attn_fwd_pair_f16(const sg_attn_desc* d0, const sg_attn_desc* 
     if (int rc = attn_params(d1, p1, "sg_attn_fwd_pair_f16[1]")) return rc;
     const SgOptions& opt = sg_options();
     const bool same = d0->D == d1->D && d0->B == d1->B && d0->H == d1->H && d0->Nq == d1->Nq;   // (short K/V rows: either problem)
-    const bool defaults = !opt.attn_sub2 && !opt.attn_prio && opt.attn_d80 == 1 && opt.attn_d160 >= 3 &&
-                          !(d0->D == 40 && opt.attn_d40_loop == 1);
+    const bool defaults = !(d0->D == 40 && opt.attn_d40_loop == 1);
     if (!same || !defaults) {
         if (int rc = attn_fwd(d0, nullptr, stream)) return rc;
         return attn_fwd(d1, nullptr, stream);

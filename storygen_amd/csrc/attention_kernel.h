@@ -49,27 +49,23 @@ __device__ __forceinline__ int kswz(int row) {
 constexpr int F40_KPAD = 2688;       // bytes in front of the ring: 16-byte constants at 0 and 32 * 80 (the two 32-key blocks)
 constexpr int F40_ONES = 128;        // bytes behind every tile image: one V^T row of ones
 
-// LDS of one workgroup: the S-stage ring of (K tile | VT tile) images
-template <int D, int S, int SUB>
+// LDS of one workgroup: NIMG (K tile | VT tile) images — the S stages of the ring, or the NW tiles of a key-split group
+template <int D, int NIMG>
 constexpr int attn_smem_bytes() {
     // (+ 16: the general path of a head dim that is not a multiple of 16 reads one chunk past its last K row; D = 80 / 160 do not)
-    return D == 40 ? F40_KPAD + S * SUB * (KVBLK * D * 2 + D * 128 + F40_ONES) : S * SUB * (KVBLK * D * 2 + D * 128) + (D % 16 == 0 ? 0 : 16);
+    return D == 40 ? F40_KPAD + NIMG * (KVBLK * D * 2 + D * 128 + F40_ONES) : NIMG * (KVBLK * D * 2 + D * 128) + (D % 16 == 0 ? 0 : 16);
 }
 
 // One workgroup's work: `block` of `nblocks` (the launch's own numbering — a paired launch runs two problems in one grid).
-#ifdef SG_ATTN_RT_STAGE
-constexpr bool UNROLL_STAGES = false;     // A/B build (tools/ab_lib.py): the ring stage as a run-time variable, as in rounds 1-4
-#else
-constexpr bool UNROLL_STAGES = true;
-#endif
-
+//
 // KSPLIT (round 5; D = 160, the 16x16 / 8x8 levels): the NW waves of a workgroup share ONE block of 32 queries and split its KEYS — a
 // group of NW tiles is loaded into the single ring stage by all waves, wave w computes tile w of it, and the partial (max, sum, O^T)
 // of the waves are merged through LDS at the end.  At Nq <= 256 the plain decomposition leaves 24 - 48 workgroups walking 12-tile
 // chains at ~5 k cycles per tile (one wave per SIMD: nothing hides the LDS and DMA latencies of a 40 KB tile); splitting the keys
 // across the waves shortens that chain NW-fold for the price of an unpipelined ring (S = 1: load, barrier, compute, barrier).
-template <int D, int NW, int S, int SUB, bool PRIO, bool LSE, bool LEAN = false, bool GENERAL = false, bool KSPLIT = false>
+template <int D, int NW, int S, bool LSE, bool LEAN = false, bool GENERAL = false, bool KSPLIT = false>
 __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, char* smem, const int block, const int nblocks) {
+    constexpr int SUB = KSPLIT ? NW : 1;        // tiles per ring stage (key split: one per wave)
     constexpr bool F40 = D == 40 && !GENERAL;   // softmax bookkeeping in the padded head dimension (see F40_KPAD)
     constexpr int DC = D / 8;                   // 16-byte chunks per K row
     constexpr int NDK = (D + 15) / 16;          // MFMA k-steps of S^T (contraction padded to 16)
@@ -79,15 +75,14 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, char* smem, c
     constexpr int V_BYTES = D * 128;
     constexpr int K_SEG = K_BYTES / 1024, V_SEG = V_BYTES / 1024, NSEG = K_SEG + V_SEG;   // 1 KiB = one wave DMA
     constexpr int TSTAGE = K_BYTES + V_BYTES + (F40 ? F40_ONES : 0);   // LDS image of one 64-key tile
-    constexpr int STAGE = SUB * TSTAGE;         // a ring stage holds SUB consecutive tiles: one barrier per SUB tiles
+    constexpr int STAGE = SUB * TSTAGE;
     constexpr int RING0 = F40 ? F40_KPAD : 0;   // byte offset of the ring
     constexpr int MAXL = (NSEG + NW - 1) / NW;  // DMA instructions per tile of the busiest wave
     constexpr int REM = NSEG % NW;              // waves < REM issue MAXL, the others MAXL - 1 (REM == 0: all MAXL)
-    static_assert(KSPLIT ? (S == 1 && SUB == NW && !LSE && !(D == 40 && !GENERAL)) : (S == 2 || S == 3), "2 or 3 stages; key split: one stage of NW tiles");
-    static_assert(KSPLIT || SUB == 1 || S == 2, "multi-tile stages use the 2-stage ring (plain vmcnt(0) waits)");
+    static_assert(KSPLIT ? (S == 1 && !LSE && !(D == 40 && !GENERAL)) : (S == 2 || S == 3), "2 or 3 stages; key split: one stage of NW tiles");
     static_assert(!KSPLIT || NW * (8 + DT * 64) * 64 <= S * SUB * (KVBLK * D * 2 + D * 128), "the merge images of the waves fit the dead ring");
     static_assert((S - 1) * MAXL < 64, "vmcnt is a 6-bit counter");
-    static_assert(RING0 + S * STAGE + (F40 || D % 16 == 0 ? 0 : 16) <= attn_smem_bytes<D, S, SUB>(), "LDS size");
+    static_assert(RING0 + S * STAGE + (F40 || D % 16 == 0 ? 0 : 16) <= attn_smem_bytes<D, S * SUB>(), "LDS size");
     static_assert(!F40 || (32 * KROW + 16 <= F40_KPAD && F40_KPAD % 128 == 0), "K pad constants of both 32-key blocks");
 
     const int t = threadIdx.x, lane = t & 63, l31 = lane & 31, hi = lane >> 5;
@@ -225,10 +220,10 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, char* smem, c
     const int prow = (l31 & ~12) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);          // pi(l31): swap bits 2 and 3
     // The ring stage is a compile-time constant inside the loop body (S copies of it per trip): the LDS addresses of the fragment reads
     // are then per-lane bases + immediates and the DMA destinations constants, where a run-time stage cost 16 v_add_u32 and a dozen scalar
-    // instructions per tile (UNROLL_STAGES = false: the round-1..4 loop with a run-time stage, for A/B builds).  D = 40 only — measured
+    // instructions per tile.  D = 40 only (the other head dims keep the run-time stage of rounds 1 - 4) — measured
     // -3.0 / -3.6 % per launch there (309.7 vs 319.1 us at B3 Nq 4096 Nk 12288, 152.6 vs 158.3 at B4 Nk 4096), nothing at D = 80 / 160,
     // whose tile bodies are 2 - 4x larger (profiles/r04l_attention_unrolled_stages.txt).
-    constexpr bool UNR = UNROLL_STAGES && D == 40;
+    constexpr bool UNR = D == 40;
     int rt_stage = 0;
     for (int group0 = 0; group0 < ngroups; group0 += (UNR ? S : 1)) {
 #pragma unroll
@@ -257,11 +252,13 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, char* smem, c
             issue(group + S - 1, st);
         }
         }
+        // (a one-trip loop, left from the multi-tile stages this body once had: without it the compiler allocates registers differently in
+        // every instantiation — 85 -> 106 SGPRs in the D = 40 training forward — and that code has not been measured)
 #pragma unroll
-      for (int subi = 0; subi < (KSPLIT ? 1 : SUB); ++subi) {
+      for (int subi = 0; subi < 1; ++subi) {
         const int sub = KSPLIT ? wave : subi;      // key split: this wave's tile of the group
         const int tile = group * SUB + sub;
-        if (tile < ntiles) {      // (no `break`: it keeps the per-lane arrays from being promoted to registers)
+        if (tile < ntiles) {
         const char* sK = smem + RING0 + stage * STAGE + sub * TSTAGE;
         const char* sV = sK + K_BYTES;
 
@@ -294,15 +291,11 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, char* smem, c
                 }
             }
             __builtin_amdgcn_sched_barrier(0);   // keep the loads ahead of the MFMAs (the scheduler would re-serialise them)
-            // PRIO: raise this wave's issue priority over its SIMD neighbours (other workgroups, in their softmax VALU
-            // phase) for the duration of a pure-MFMA cluster — guide T5
-            if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int st = 0; st < NDK; ++st)
                     s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[kb][st], qf[st], st == 0 ? zero16 : s[kb], 0, 0, 0);   // C = inline 0
-            if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
         } else {
             // D = 160: the K fragments of all 10 k-steps would need 80 VGPRs, so they are read per k-step — ONE k-step ahead of the MFMAs
             // that consume them (two register sets; the sched_barrier keeps the scheduler from sinking every read to just before its
@@ -430,11 +423,9 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, char* smem, c
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int i = 0; i < DT; ++i)
                 oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[VPRE ? ks : 0][i], pf, oacc[i], 0, 0, 0);
-            if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
             if constexpr (!VPRE) {
                 if (ks + 1 < 4) {
 #pragma unroll
@@ -443,7 +434,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, char* smem, c
             }
         }
         }
-      }   // sub-tiles of the group
+      }
         }
         if (!UNR && ++rt_stage == S) rt_stage = 0;
     }
@@ -525,7 +516,7 @@ __device__ __forceinline__ void attn_d40_body(const AttnParams& p, char* smem, c
     constexpr int NPAIR = (K_SEG - 1) / NW;     // (K, V^T) segment pairs per wave and tile
     static_assert((NW == 2 || NW == 4) && (S == 2 || S == 3), "2 or 4 waves, 2 or 3 stages");
     static_assert(K_SEG == 5 && V_SEG == 5 && NPAIR * NW == 4, "4 segments of K and of V^T over the waves + one of each for waves 0 and 1");
-    static_assert(RING0 + S * TSTAGE <= attn_smem_bytes<D, S, 1>(), "LDS size");
+    static_assert(RING0 + S * TSTAGE <= attn_smem_bytes<D, S>(), "LDS size");
 
     const int t = threadIdx.x, lane = t & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -804,14 +795,14 @@ __device__ __forceinline__ void attn_d40_body(const AttnParams& p, char* smem, c
 
 template <int NW, int S>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) void attn_d40_kernel(const AttnParams p) {
-    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<40, S, 1>()];
+    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<40, S>()];
     attn_d40_body<NW, S>(p, smem, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // the paired launch (attn_fwd_pair_kernel below) on the D = 40 body
 template <int NW, int S>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) void attn_d40_pair_kernel(const AttnParams a, const AttnParams b, const int na) {
-    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<40, S, 1>()];
+    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<40, S>()];
     if ((int)blockIdx.x < na) attn_d40_body<NW, S>(a, smem, (int)blockIdx.x, na);
     else attn_d40_body<NW, S>(b, smem, (int)blockIdx.x - na, (int)gridDim.x - na);
 }
@@ -831,17 +822,17 @@ void launch_attn_d40_pair(const AttnParams& a0, const AttnParams& b0, hipStream_
     hipLaunchKernelGGL((attn_d40_pair_kernel<NW, S>), dim3(na + nb), dim3(64 * NW), 0, st, a, b, na);
 }
 
-template <int D, int NW, int S, int SUB = 1, bool PRIO = false, bool LSE = false, bool LEAN = false, bool GENERAL = false>
+template <int D, int NW, int S, bool LSE = false, bool LEAN = false, bool GENERAL = false>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnParams p) {
-    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<D, S, SUB>()];
-    attn_fwd_body<D, NW, S, SUB, PRIO, LSE, LEAN, GENERAL>(p, smem, (int)blockIdx.x, (int)gridDim.x);
+    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<D, S>()];
+    attn_fwd_body<D, NW, S, LSE, LEAN, GENERAL>(p, smem, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // key-split instantiation (KSPLIT above): one workgroup = NW waves on ONE 32-query block of one (batch, head)
 template <int D, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_ksplit_kernel(const AttnParams p) {
-    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<D, 1, NW>()];
-    attn_fwd_body<D, NW, 1, NW, false, false, false, false, true>(p, smem, (int)blockIdx.x, (int)gridDim.x);
+    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<D, NW>()];
+    attn_fwd_body<D, NW, 1, false, false, false, true>(p, smem, (int)blockIdx.x, (int)gridDim.x);
 }
 
 template <int D, int NW>
@@ -856,16 +847,16 @@ void launch_attn_ksplit(const AttnParams& p0, hipStream_t st) {
 // CUs that a's tail leaves idle.
 template <int D, int NW, int S>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_pair_kernel(const AttnParams a, const AttnParams b, const int na) {
-    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<D, S, 1>()];
-    if ((int)blockIdx.x < na) attn_fwd_body<D, NW, S, 1, false, false>(a, smem, (int)blockIdx.x, na);
-    else attn_fwd_body<D, NW, S, 1, false, false>(b, smem, (int)blockIdx.x - na, (int)gridDim.x - na);
+    __shared__ __attribute__((aligned(16))) char smem[attn_smem_bytes<D, S>()];
+    if ((int)blockIdx.x < na) attn_fwd_body<D, NW, S, false>(a, smem, (int)blockIdx.x, na);
+    else attn_fwd_body<D, NW, S, false>(b, smem, (int)blockIdx.x - na, (int)gridDim.x - na);
 }
 
-template <int D, int NW, int S, int SUB = 1, bool PRIO = false, bool LSE = false, bool LEAN = false, bool GENERAL = false>
+template <int D, int NW, int S, bool LSE = false, bool LEAN = false, bool GENERAL = false>
 void launch_attn(const AttnParams& p0, hipStream_t st) {
     AttnParams p = p0;
     p.nqb = sg_cdiv(p.Nq, 32 * NW);
-    hipLaunchKernelGGL((attn_fwd_kernel<D, NW, S, SUB, PRIO, LSE, LEAN, GENERAL>), dim3(p.nqb * p.H * p.B), dim3(64 * NW), 0, st, p);
+    hipLaunchKernelGGL((attn_fwd_kernel<D, NW, S, LSE, LEAN, GENERAL>), dim3(p.nqb * p.H * p.B), dim3(64 * NW), 0, st, p);
 }
 
 template <int D, int NW, int S>

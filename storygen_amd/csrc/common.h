@@ -48,7 +48,8 @@ struct SgOptions {
     int big_m = 0, big_bm = 0, big_bn = 0; // big_m > 0: launches of M >= big_m rows without a tile hint take the (big_bm, big_bn) tile — the batched reference pass on smaller workgroups (A/B: how long a CU is held matters to the co-running main pass)
     int fat_m = 0;                         // > 0: convolutions of M >= fat_m rows take the 128x64-per-wave tiles (mma_fat_kernel: 512x128 / 256x256) when no tile is hinted
     int lat_wide = 0, lat_wide_m = 256;   // 1: M <= lat_wide_m (the 8x8 level) takes the 64x128-tile / 6-stage weight-streaming form (measured neutral: default off; tile hint (64, 128, 8) selects it per launch)
-    int attn_sub2 = 0, attn_prio = 0, attn_d80 = 1, attn_d160 = 4 /* 4: key-split workgroups at Nq <= 256 */, attn_lean = 0;
+    int attn_d160 = 4;                 // D = 160 attention: 4 = key-split workgroups at Nq <= 256, 3 = always the query-split kernel
+    int attn_lean = 0;
     int attn_d40_general = 0;          // 1 = the D = 40 launches use the general softmax path (A/B against the padded-dimension fast path)
     int attn_d40_loop = 0;             // 1 = the D = 40 inference launches run the shared tile loop of attn_fwd_body instead of attn_d40_body (A/B, bit-identical)
     int gn_no_fused = 0, gn_wide = 1;

@@ -152,32 +152,15 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #define EPI_PRE_ARGS pre_f, pre_bias
 #define EPI_PRE_PARAMS f32x4 (&pre)[16], u32x2& pbias
 
-// Epilogue traffic is streamed once (outputs written, residuals read): with SG_EPI_NT the accesses carry the non-temporal hint, so
-// they do not evict the operand panels (weights, im2col rows re-read by every tap and column tile) from the XCD's 4 MB L2 — the PMC
-// pass of round 4 measured 150 MB of fabric traffic per 64x64 320->320 convolution against 58 MB of compulsory traffic.
+// Epilogue traffic is streamed once (outputs written, residuals read) as plain 16- / 8-byte accesses: the non-temporal hint on them was
+// measured and not adopted (GEMM family -0.18 ms, GroupNorm +0.11, step equal: HISTORY.md).
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void st_stream(float* p, const f32x4& v) {
-#ifdef SG_EPI_NT
-    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-#else
-    *reinterpret_cast<f32x4*>(p) = v;
-#endif
-}
+__device__ __forceinline__ void st_stream(float* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
 __device__ __forceinline__ void st_stream(f16* p, const uint2& v) {
     const u32x2v w = {v.x, v.y};
-#ifdef SG_EPI_NT
-    __builtin_nontemporal_store(w, reinterpret_cast<u32x2v*>(p));
-#else
     *reinterpret_cast<u32x2v*>(p) = w;
-#endif
 }
-__device__ __forceinline__ f32x4 ld_stream(const float* p) {
-#ifdef SG_EPI_NT
-    return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-#else
-    return *reinterpret_cast<const f32x4*>(p);
-#endif
-}
+__device__ __forceinline__ f32x4 ld_stream(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // Everything the fused linear epilogue needs from memory that does not depend on the accumulators is requested early — during the
 // last K slab — into registers: the fp32 residual (the UNet's residual stream) in the row-quad layout (16 B per item; rowq = first
@@ -915,20 +898,18 @@ __global__ __launch_bounds__(256) void mma_kernel(const MmaParams p) {
 // slab t-1, whose stage it overwrites.
 // One LDS-DMA piece (1 KiB per wave): 16 bytes per lane from `base` (wave-uniform) + `offb` (per-lane BYTE offset, < 2^32: the host
 // validates element offsets < 2^31) to the wave-uniform LDS address `lds_wave_base` (+ lane * 16, the hardware's lane-linear image).
-// SG_GLDS_SADDR (A/B build): the scalar-base form of the instruction, written out — the builtin always materialises a 64-bit per-lane
-// address (one v_lshl_add_u64 per piece beside the MFMAs).  Every piece of a kernel must then go through here (M0 is set by hand).
+// (The builtin always materialises a 64-bit per-lane address, one v_lshl_add_u64 per piece beside the MFMAs; the scalar-base form of the
+// instruction written out by hand measured negative: profiles/r06bh_lds_dma_scalar_base_form_NEGATIVE.txt.  LdsRef::a served that form
+// and nothing reads it now, but without it the compiler allocates the registers of the 4-wave kernels differently, and that code has
+// not been measured: it goes with the next change that re-measures them.)
 struct LdsRef { char* p; unsigned a; };          // one LDS location as a generic pointer and as its LDS byte address
 __device__ __forceinline__ LdsRef operator+(LdsRef r, int d) { return LdsRef{r.p + d, r.a + (unsigned)d}; }
 __device__ __forceinline__ LdsRef lds_ref(char* smem) {
     return LdsRef{smem, (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned long)((__attribute__((address_space(3))) char*)smem))};
 }
 __device__ __forceinline__ void glds16(const f16* base, unsigned offb, LdsRef dst) {
-#ifdef SG_GLDS_SADDR
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(offb), "s"(base), "s"(dst.a) : "memory");
-#else
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(base) + offb),
                                      (__attribute__((address_space(3))) void*)dst.p, 16, 0, 0);
-#endif
 }
 
 template <int N>
@@ -995,11 +976,7 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
     // 256x64 40.6 -> 37.4).  The 8-wave 256x128 tile (two waves per SIMD cover each other) measured +3 ... +6 % and keeps the burst.
     // There the two waves of a SIMD leave the barrier together and would burst together: waves 4 - 7 issue theirs behind the THIRD k-step
     // instead (STAGGER: conv 64^2 640->320 92.8 -> 85.5 us, 64^2 320->320 49.3 -> 47.4, 16^2 / 32^2 -2 %, profiles/r04r_*).
-#ifdef SG_PIPE_BURST
-    constexpr bool SPREAD = false, STAGGER = false;       // A/B build (tools/ab_lib.py): rounds 1-4, every wave bursts behind the first k-step
-#else
     constexpr bool SPREAD = (NW <= 4 || WT == 1) && !PROF, STAGGER = NW == 8 && WT == 2 && !PROF;
-#endif
     static_assert(S >= 2 && S <= 8, "ring depth");
     static_assert(WT == 2 || (WGM % 2 == 0 && WGN % 2 == 0), "32x32 waves come in 2x2 groups (epi_finish_q)");
     static_assert((S - 1) * LPT < 64, "vmcnt is a 6-bit counter");
@@ -1029,23 +1006,19 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
         w_off[i] = 2u * (unsigned)((long)min(n0 + row, p.N - 1) * p.ldw + lc * 8);       // bytes
     }
     // `sel` < 0: every piece; otherwise only the pieces whose running index (A pieces first, then W) is sel modulo 4 — the refill of a
-    // slab spread over its four k-steps (SG_PIPE_SPREAD builds)
+    // slab spread over its four k-steps (SPREAD above)
     // K order of the CONVOLUTION (round 5): slab kt = (channel block kt / 9, tap kt % 9) — the nine taps of one 64-channel block are
     // consecutive slabs.  They re-read the same input pixels (shifted by one): with the taps innermost that working set is one channel
     // block of the tile's pixels per workgroup (~40 KB; ~1.2 MB for the workgroups of an XCD) and stays in the XCD's 4 MB L2, where the
     // former order (tap kt / cpt outermost, all channel blocks inside) walked the whole input panel between two taps and re-fetched it
     // from the fabric nine times (profiles/traffic.json of the round-5 mid build: 1 053 MB per launch against 79 MB algorithmic for
     // the batch-20 16x16 convolutions).  The weights are [Cout][ky][kx][Cin]: slab kt starts at element (kt % 9) * Cin + (kt / 9) * 64
-    // of a row — either order is a plain offset, nothing is repacked.  -DSG_CONV_TAP_MAJOR rebuilds the former order (A/B builds).
+    // of a row — either order is a plain offset, nothing is repacked.
     // GEMM: slab kt starts at element kt * 64 of both operands.
     auto w_koff = [&](int kt) __attribute__((always_inline)) -> long {
         if constexpr (CONV) {
-#ifdef SG_CONV_TAP_MAJOR
-            return (long)kt * BK;
-#else
             const int cc = (kt * 7282) >> 16, tap = kt - 9 * cc;        // kt / 9 for kt < 3 000 (validated on the host)
             return (long)tap * p.cpt * BK + (long)cc * BK;
-#endif
         } else {
             return (long)kt * BK;
         }
@@ -1095,11 +1068,7 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
         r.ky = r.kx = 0;
         r.wk = w_koff(kt);
         if constexpr (CONV) {
-#ifdef SG_CONV_TAP_MAJOR
-            const int tap = (int)fd_div((unsigned)kt, p.fd_cpt), cc = kt - tap * p.cpt;
-#else
             const int cc = (kt * 7282) >> 16, tap = kt - 9 * cc;
-#endif
             const int ky = (tap * 11) >> 5, kx = tap - ky * 3;           // tap / 3 for tap < 9
             r.ky = ky; r.kx = kx;
             r.At = !p.ups ? p.A + ((long)(ky * wp + kx) * p.lda + cc * BK) : p.A + cc * BK;
@@ -1130,53 +1099,24 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
                 if (sel < 0 || (i & 3) == sel) glds16(ab.At, a_off[i], sA + i * ISTR);
         }
     };
-#ifdef SG_PIPE_BASE_DIV        // A/B build (tools/ab_lib.py): every slab's base from its index (multiply-shift division + 64-bit products)
-    auto a_next = [&](int kt) __attribute__((always_inline)) { return a_base(kt); };
-#else
-    // The slabs of a block are requested in order (kt0, kt0 + 1, ...): their operand bases come from running counters — channel block,
-    // tap column, tap row, element offset — instead of a division and a 64-bit product per slab (≈ 45 -> ≈ 10 scalar instructions in
-    // front of every refill; the refill of the 256x128 tile is a burst right behind them)
+    // The slabs of a block are requested in order (kt0, kt0 + 1, ...): their operand bases come from running counters — tap column, tap
+    // row, element offset — instead of a division and a 64-bit product per slab (≈ 45 -> ≈ 10 scalar instructions in front of every
+    // refill; the refill of the 256x128 tile is a burst right behind them).  a_base serves the first slab only.
     long it_off, it_wk;
-#ifdef SG_CONV_TAP_MAJOR
-    int it_cc = 0;
-#endif
     int it_kx = 0, it_ky = 0;
     {
         const ABase b0 = a_base(kt0);
         it_off = b0.At - p.A;
         it_wk = b0.wk;
-        if constexpr (CONV) {
-#ifdef SG_CONV_TAP_MAJOR
-            const int tap = (int)fd_div((unsigned)kt0, p.fd_cpt);
-            it_cc = kt0 - tap * p.cpt;
-#endif
-            it_ky = b0.ky; it_kx = b0.kx;
-        }
+        if constexpr (CONV) { it_ky = b0.ky; it_kx = b0.kx; }
     }
-#ifdef SG_CONV_TAP_MAJOR
-    const long it_dx = CONV ? (p.ups ? 0 : (long)p.lda) - (long)p.cpt * BK : 0;       // next tap column: one pixel right, channel block 0
-    const long it_dy = CONV && !p.ups ? (long)(wp - 3) * p.lda : 0;                    // ... next tap row: from column 3 back to 0, one row down
-    auto a_next = [&](int) __attribute__((always_inline)) {
-        ABase r;
-        r.At = p.A + it_off; r.ky = it_ky; r.kx = it_kx; r.wk = it_wk;
-        it_off += BK; it_wk += BK;
-        if constexpr (CONV) {
-            if (++it_cc == p.cpt) {
-                it_cc = 0;
-                it_off += it_dx;
-                if (++it_kx == 3) { it_kx = 0; ++it_ky; it_off += it_dy; }
-            }
-        }
-        return r;
-    };
-#else
     // taps innermost: one pixel right per slab; after column 2 one row down and back to column 0; after tap 8 back to tap 0 of the
     // next channel block.  (Nearest-2x upsampling: the pixel offset comes from (ky, kx) in a_emit, only the channel block moves here.)
     const long it_px = CONV && !p.ups ? (long)p.lda : 0;
     const long it_dy = CONV && !p.ups ? (long)(wp - 3) * p.lda : 0;
     const long it_dc = CONV ? (p.ups ? 0 : -3L * wp * p.lda) + BK : 0;
     const long it_wtap = CONV ? (long)p.cpt * BK : BK, it_wdc = CONV ? BK - 9L * p.cpt * BK : 0;
-    auto a_next = [&](int) __attribute__((always_inline)) {
+    auto a_next = [&]() __attribute__((always_inline)) {
         ABase r;
         r.At = p.A + it_off; r.ky = it_ky; r.kx = it_kx; r.wk = it_wk;
         it_wk += it_wtap;
@@ -1191,18 +1131,16 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
         }
         return r;
     };
-#endif
-#endif
     // (A pieces of a slab, then its W pieces: one a_next per slab, in slab order)
-    auto issue_aw = [&](int kt, int stage, bool with_w) __attribute__((always_inline)) {
-        const ABase ab = a_next(kt);
+    auto issue_aw = [&](int stage, bool with_w) __attribute__((always_inline)) {
+        const ABase ab = a_next();
         a_emit(ab, stage, -1);
         if (with_w) issue_w(ab.wk, stage);
     };
-    if (nt > 0) issue_aw(kt0, 0, false);                   // (its weights left first, above)
+    if (nt > 0) issue_aw(0, false);                   // (its weights left first, above)
 #pragma unroll
     for (int st = 1; st < S - 1; ++st)
-        if (nt > st) issue_aw(kt0 + st, st, true);
+        if (nt > st) issue_aw(st, true);
 
     f32x16 acc[WTM][WTN];
 #pragma unroll
@@ -1277,7 +1215,7 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
         int rst = stage + S - 1;
         if (rst >= S) rst -= S;
         ABase ab = {nullptr, 0, 0, 0};
-        if (refill) ab = a_next(kt0 + it + S - 1);
+        if (refill) ab = a_next();
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             if (ks + 1 < 4) load_frags((ks + 1) & 1, ks + 1);
@@ -1297,7 +1235,7 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
                 if constexpr (LAST) {
                     prefetch();
                 } else if (it + S - 1 < nt) {
-                    issue_aw(kt0 + it + S - 1, rst, true);
+                    issue_aw(rst, true);
                 }
                 stamp(5);
             }
@@ -1315,17 +1253,7 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
     // — counted vmcnt waits need the number at compile time, so each of them is its own copy of the slab (run-time stage).
     constexpr int TAIL = S > 2 ? S - 2 : 1, YS = S - 2;
     const int nsteady = nt > TAIL ? nt - TAIL : 0;
-#ifdef SG_PIPE_RT_STAGE          // A/B build (tools/ab_lib.py): the ring stage as a run-time variable, as in rounds 1-4
-    {
-        int stage = 0;
-        for (int it = 0; it < nsteady; ++it) {
-            slab(it, std::false_type{}, std::integral_constant<int, YS>{}, stage);
-            if (++stage == S) stage = 0;
-        }
-    }
-#else
     for (int it = 0; it < nsteady; it += S) slab_seq<0, S, YS>(slab, it, nsteady);
-#endif
     slab_tail<TAIL - 1, S>(slab, nt);
     if (nt <= 0) prefetch();
     if constexpr (WT == 2) epi_finish<WGM, WGN, WTM>(p, smem, acc, pre_f, pre_bias, m0, n0, z, wave, wm, wn, lane);

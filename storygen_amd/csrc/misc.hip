@@ -16,14 +16,15 @@ extern "C" int sg_debug_set_option(const char* name, int64_t value) {
     SgOptions& o = sg_options();
     struct Entry { const char* n; int* p; };
     const Entry table[] = {{"tile_m", &o.tile_m}, {"tile_n", &o.tile_n}, {"no_pipe", &o.no_pipe}, {"no_split", &o.no_split},
-                           {"no_nmajor", &o.no_nmajor}, {"attn_sub2", &o.attn_sub2}, {"attn_prio", &o.attn_prio},
-                           {"attn_d80", &o.attn_d80}, {"attn_d160", &o.attn_d160}, {"gn_no_fused", &o.gn_no_fused},
+                           {"no_nmajor", &o.no_nmajor}, {"attn_d160", &o.attn_d160}, {"gn_no_fused", &o.gn_no_fused},
                            {"gn_wide", &o.gn_wide}, {"attn_lean", &o.attn_lean}, {"attn_d40_general", &o.attn_d40_general}, {"attn_d40_loop", &o.attn_d40_loop},
                            {"gn_fused_nt", &o.gn_fused_nt}, {"pipe_stages", &o.pipe_stages}, {"ff_variant", &o.ff_variant},
                            {"gn_chunks", &o.gn_chunks}, {"lat_tiles", &o.lat_tiles}, {"lat_min_kt", &o.lat_min_kt},
                            {"lat_max_kt", &o.lat_max_kt}, {"lat_stages", &o.lat_stages}, {"lat_wide", &o.lat_wide}, {"lat_mask", &o.lat_mask}, {"lat_wide_m", &o.lat_wide_m}, {"fat_m", &o.fat_m}, {"big_m", &o.big_m}, {"big_bm", &o.big_bm}, {"big_bn", &o.big_bn}};
     for (const Entry& e : table)
         if (strcmp(e.n, name) == 0) {
+            if (e.p == &o.attn_d160 && value != 3 && value != 4)
+                return sg_set_error(SG_EINVAL, "sg_debug_set_option: attn_d160 must be 3 (query split) or 4 (key split where it applies)");
             *e.p = (int)value;
             return SG_OK;
         }

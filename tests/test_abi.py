@@ -202,7 +202,7 @@ def test_no_kernel_uses_scratch_memory():
 
 def test_library_never_reads_the_environment():
     """Development options live behind sg_debug_set_option (kernel selection must not depend on environment
-    variables): no getenv in any kernel source, unknown option names are rejected, "reset" restores the defaults."""
+    variables): no getenv in any kernel source, unknown option names and values without a kernel are rejected, "reset" restores the defaults."""
     import glob
     import os
     from storygen_amd import _lib
@@ -213,6 +213,18 @@ def test_library_never_reads_the_environment():
     lib = _lib.load()
     assert lib.sg_debug_set_option(b"no_split", 1) == 0 and lib.sg_debug_set_option(b"reset", 0) == 0
     assert lib.sg_debug_set_option(b"no_such_option", 1) != 0
+
+    # the attention selectors that nothing set are retired: unknown names now, and attn_d160 keeps the two values with a kernel behind
+    # them (4 = key split where it applies, the default; 3 = always the query-split kernel)
+    SG_EINVAL = -1
+    for name in (b"attn_sub2", b"attn_prio", b"attn_d80"):
+        assert lib.sg_debug_set_option(name, 1) == SG_EINVAL, name
+    for value in (0, 1, 2):
+        assert lib.sg_debug_set_option(b"attn_d160", value) == SG_EINVAL, value
+    assert lib.sg_debug_set_option(b"attn_d160", 3) == 0 and lib.sg_debug_set_option(b"attn_d160", 4) == 0
+    assert lib.sg_debug_set_option(b"attn_d160", 3) == 0 and lib.sg_debug_set_option(b"reset", 0) == 0
+    with open(os.path.join(root, "storygen_amd", "csrc", "common.h")) as f:      # "reset" assigns SgOptions{}: its default is 4
+        assert "int attn_d160 = 4;" in f.read()
 
 
 def test_shipped_kernels_contain_no_packed_fp32_instructions(tmp_path):

@@ -251,7 +251,7 @@ def test_traffic_on_file_was_measured_on_this_build():
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "traffic.json")
     with open(path) as f:
         t = json.load(f)
-    assert t.get("kernel_source_hash") == source_hash(), "re-run the two PMC passes on the GPU box (tools/calls/r4_call21.sh) and copy traffic.json to profiles/"
+    assert t.get("kernel_source_hash") == source_hash(), "re-run the two separate PMC passes of bench.py on the GPU box, merge them with tools/traffic_from_pmc.py and copy traffic.json to profiles/"
     assert t["kernels"]["mma_pipe_body (gemm + conv3x3: mma_pipe_kernel / mma_lat_kernel)"]["hbm_bytes_per_launch"] > 0
 
 

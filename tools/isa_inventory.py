@@ -2,7 +2,7 @@
 """Static instruction inventory of a kernel's loops (development tool; CPU only: hipcc cross-compiles gfx950).
 Compiles one csrc/*.hip to assembly, finds the named kernel, and prints for every loop (backward branch) the instruction mix —
 MFMA / transcendental / other VALU / LDS / vector memory / SALU — and the VALU opcode histogram of loops that contain MFMAs.
-Usage: python tools/isa_inventory.py attention.hip attn_fwd_kernelILi40ELi4ELi3ELi1ELb0ELb0E [extra hipcc flags...]
+Usage: python tools/isa_inventory.py attention.hip attn_fwd_kernelILi40ELi4ELi3ELb0ELb0E [extra hipcc flags...]
 (attention sources need `-mllvm -amdgpu-mfma-vgpr-form=1`, as in storygen_amd/build.py)"""
 import os
 import re
