@@ -65,6 +65,15 @@ int          sg_device_cus(void);
  * by a second kernel that applies the epilogue).  split_k == 0 lets the library choose: it only considers
  * splits whose partial tiles fit the workspace it was given (M*N*4 bytes per split), so any fixed scratch
  * buffer — or NULL to forbid splitting — is valid; sg_gemm_workspace_bytes(M, N, 0) is the most it can use.
+ * A forced split_k in [2, 64] is honoured as given on the pipelined, latency and register-staged kernels and on every tile of theirs
+ * (it never changes their tile choice).  The one exception: the eight-wave 512x128 / 256x256 kernels do not split K, so such a tile
+ * hint together with split_k > 1 is dropped and the library chooses as if no tile had been asked for, on the forced slice count.  The count is
+ * clamped to the number of 64-deep K slabs, ceil(K / 64), where it is larger; sg_gemm_launch_plan / sg_conv3x3_planned_splits
+ * report the count the launch uses, and a workspace of M*N*4 bytes per reported slice is enough.  Slice z owns the slabs
+ * [z, z + 1) * ceil(slabs / split_k): the last slices may own none and contribute zeros.  Values outside [0, 64] are SG_EINVAL.
+ * Operand size: the pipelined kernels address A and W through 32-bit byte offsets, so the last element of each must lie within
+ * 2^31 elements (4 GiB) of its base pointer: (M - 1) * lda + K <= 2^31 and (N - 1) * ldw + K <= 2^31, else SG_EINVAL.  Outputs,
+ * residuals, biases and the workspace are addressed with 64 bits.
  */
 #define SG_EPI_LINEAR 0
 #define SG_EPI_GEGLU  1
@@ -87,7 +96,7 @@ typedef struct sg_gemm_desc {
     const float*   rowbias;           /* fp32 [batches, rowbias_ld] or NULL */
     int64_t        rowbias_ld;
     int32_t        rows_per_batch;    /* rows of A per rowbias row (>=1) */
-    int32_t        split_k;           /* 0 = auto, 1 = none, >1 = forced */
+    int32_t        split_k;           /* 0 = auto, 1 = none, 2..64 = forced (clamped to ceil(K / 64), see above) */
     int32_t        tile_m, tile_n;    /* 0, 0 = library heuristic; else one of 256x128, 128x128, 256x64, 128x64, 64x128,
                                          64x64 (a tuning hint: results are identical up to fp32 summation order) */
     int32_t        tile_waves;        /* 0, or the tile's wave count: 64x64 per wave = (tile_m/64)*(tile_n/64); round 6: 4 with a 64x64 tile /
@@ -172,6 +181,8 @@ size_t sg_gemm_workspace_bytes(int32_t M, int32_t N, int32_t split_k);
  * x_padded = 1: `x` is the start of a buffer [B, H+2, W+2, Cin] whose one-pixel border is zero (interior pixel
  * (y, x) at row y+1, column x+1).  Padding then needs no predicate and the kernel streams its tiles with LDS-DMA
  * through a multi-stage pipeline; x_padded = 0 reads an unpadded [B, H, W, Cin] tensor with bounds checks.
+ * Operand size (32-bit byte offsets, as for sg_gemm_desc): (pixels - 1) * ldx + Cin <= 2^31 elements, where pixels =
+ * B * (H + 2) * (W + 2) with x_padded and B * H * W without, and Cout * 9 * Cin <= 2^31; else SG_EINVAL.
  */
 typedef struct sg_conv3x3_desc {
     const sg_half* x;  int64_t ldx;   /* [B, H, W, Cin], pixel stride ldx */

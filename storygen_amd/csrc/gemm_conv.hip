@@ -897,7 +897,7 @@ __global__ __launch_bounds__(256) void mma_kernel(const MmaParams p) {
 // barrier that (a) publishes slab t (every wave waited for its own DMA with a counted vmcnt first) and (b) retires every wave's reads of
 // slab t-1, whose stage it overwrites.
 // One LDS-DMA piece (1 KiB per wave): 16 bytes per lane from `base` (wave-uniform) + `offb` (per-lane BYTE offset, < 2^32: the host
-// validates element offsets < 2^31) to the wave-uniform LDS address `lds_wave_base` (+ lane * 16, the hardware's lane-linear image).
+// validates that every operand ends below 2^31 elements from its base, gemm_params) to the wave-uniform LDS address `lds_wave_base` (+ lane * 16, the hardware's lane-linear image).
 // (The builtin always materialises a 64-bit per-lane address, one v_lshl_add_u64 per piece beside the MFMAs; the scalar-base form of the
 // instruction written out by hand measured negative: profiles/r06bh_lds_dma_scalar_base_form_NEGATIVE.txt.  LdsRef::a served that form
 // and nothing reads it now, but without it the compiler allocates the registers of the 4-wave kernels differently, and that code has
@@ -1578,7 +1578,12 @@ Plan choose_plan(int M, int N, int KT, int force_split, int max_ws_split, bool p
     static const int split_opts[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16};
     const int ncand = pipe ? 6 : 1;
     const double CUS = 256.0, BW = pipe ? 18.5 : 12.0;
-    Plan best{64, 64, 1, 0};
+    // A forced split (sg_gemm_desc.split_k > 1) is honoured as given on both candidate lists — any value of [2, 64], not only those the
+    // cost model enumerates for itself — and clamped to the number of K slabs.  Slice z owns slabs [z, z + 1) * ceil(KT / s): where
+    // ceil(KT / s) * (s - 1) >= KT the last slices own none and write zero partial tiles (the mainloops' `nt > 0` / `kt0 < kt1` guards).
+    const int forced = force_split > 0 ? (force_split > KT ? KT : force_split) : 0;
+    const int gen_bm = cand_gen[0][0], gen_bn = cand_gen[0][1];
+    Plan best{pipe ? 64 : gen_bm, pipe ? 64 : gen_bn, forced ? forced : 1, 0};
     double best_cost = 1e300;
     for (int ci = 0; ci < ncand; ++ci) {
         const int bm = pipe ? cand_pipe[ci][0] : cand_gen[ci][0], bn = pipe ? cand_pipe[ci][1] : cand_gen[ci][1];
@@ -1588,8 +1593,8 @@ Plan choose_plan(int M, int N, int KT, int force_split, int max_ws_split, bool p
         const double waves_per_block = pipe ? (bm / 64) * (bn / 64) : 4.0;
         const double mfma_per_slab = pipe ? 512.0 : 512.0 * (bm / 64.0) * (bn / 64.0) / 4.0;
         for (int s : split_opts) {
-            if (force_split > 0 && s != force_split) continue;
-            if (force_split <= 0 && s > 1 && (s > max_ws_split || KT / s < 2 || g_tune.no_split)) continue;
+            if (forced) s = forced;
+            else if (s > 1 && (s > max_ws_split || KT / s < 2 || g_tune.no_split)) continue;
             if (s > KT) continue;
             const double blocks = (double)tiles * s;
             const double slabs = sg_cdiv(KT, s);
@@ -1600,9 +1605,10 @@ Plan choose_plan(int M, int N, int KT, int force_split, int max_ws_split, bool p
             double cost = (t_bw > t_mfma ? t_bw : t_mfma) + 2500.0 + blocks_per_cu * (bm * bn / 16.0);
             if (s > 1) cost += 5000.0 + (double)M * N * 4.0 * (s + 1) / 1500.0;   // second launch + partial tiles
             if (cost < best_cost) { best_cost = cost; best = Plan{bm, bn, s, 0}; }
+            if (forced) break;
         }
     }
-    if (best_cost == 1e300) best = Plan{64, 64, force_split > KT ? KT : (force_split > 0 ? force_split : 1), 0};
+    // (best_cost == 1e300: a development tile that is none of the candidates — `best` still holds a tile its family has)
     return best;
 }
 
@@ -1897,10 +1903,23 @@ int gemm_params(const sg_gemm_desc* d, MmaParams& p, const char* who) {
     SG_REQUIRE(!d->bias || sg_aligned16(d->bias), "%s: bias must be 16-byte aligned", who);
     SG_REQUIRE(!d->rowbias || (sg_aligned16(d->rowbias) && d->rowbias_ld % 4 == 0 && d->rows_per_batch >= 1),
                "%s: rowbias alignment / rows_per_batch", who);
-    SG_REQUIRE(d->split_k >= 0 && d->split_k <= 64, "%s: bad split_k %d", who, d->split_k);
+    SG_REQUIRE(d->split_k >= 0 && d->split_k <= 64, "%s: split_k %d is outside the supported range [0, 64] (0 = auto, 1 = none)", who, d->split_k);
     SG_REQUIRE(!d->workspace || (sg_aligned16(d->workspace)), "%s: workspace alignment", who);
-    SG_REQUIRE((int64_t)d->M * d->lda < (1ll << 32) && (int64_t)d->N * d->ldw < (1ll << 32),
-               "%s: operands larger than 2^32 elements are not supported (32-bit DMA offsets)", who);
+    // Addressing widths of the kernels behind this descriptor.
+    //   32-bit BYTE offsets: the per-lane LDS-DMA offsets of the pipelined, latency and fat-wave mainloops (mma_pipe_body: a_off / w_off
+    //     = 2 * (row * ld + chunk), for the convolution 2 * (pixel of tap (0, 0) * ldx + chunk), plus 2 * (dy * row pitch + dx * ldx) of
+    //     the nearest-2x gather; glds16 adds them to a 64-bit wave-uniform base).  Every one of them addresses an element of the
+    //     operand, so they are exact as long as the operand's LAST byte lies below 4 GiB from its base pointer.
+    //   64-bit: the wave-uniform slab bases (A + kt * 64, the convolution's tap / channel-block offsets), every address of the
+    //     register-staged kernel, and everything the epilogues and the split-K passes touch (C, C2, res1, res2, rowbias, workspace,
+    //     stats, LayerNorm partials: (long) row * ld or size_t products).
+    // The bound is checked for every launch, whichever family the plan then picks (the plan depends on development options).
+    const long long lim = 1ll << 31;      // elements = 4 GiB of fp16
+    const long long a_span = (long long)(d->M - 1) * d->lda + d->K, w_span = (long long)(d->N - 1) * d->ldw + d->K;
+    SG_REQUIRE(d->lda <= lim && a_span <= lim,
+               "%s: operand A spans %lld elements ((M - 1) * lda + K); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)", who, a_span);
+    SG_REQUIRE(d->ldw <= lim && w_span <= lim,
+               "%s: operand W spans %lld elements ((N - 1) * ldw + K); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)", who, w_span);
     p = MmaParams{};
     p.A = reinterpret_cast<const f16*>(d->A); p.lda = d->lda;
     p.W = reinterpret_cast<const f16*>(d->W); p.ldw = d->ldw;
@@ -2000,11 +2019,23 @@ extern "C" int sg_conv3x3_nhwc_f16(const sg_conv3x3_desc* d, sg_stream_t stream)
     if (int rc = check_out_res("sg_conv3x3", d->flags, d->y, d->ldy, nullptr, 0, d->res1, d->ldr1, nullptr, 0, d->Cout)) return rc;
     SG_REQUIRE(!d->bias || sg_aligned16(d->bias), "sg_conv3x3: bias alignment");
     SG_REQUIRE(!d->rowbias || (sg_aligned16(d->rowbias) && d->rowbias_ld % 4 == 0), "sg_conv3x3: rowbias alignment");
-    SG_REQUIRE(d->split_k >= 0 && d->split_k <= 64, "sg_conv3x3: bad split_k %d", d->split_k);
+    SG_REQUIRE(d->split_k >= 0 && d->split_k <= 64, "sg_conv3x3: split_k %d is outside the supported range [0, 64] (0 = auto, 1 = none)", d->split_k);
     SG_REQUIRE(!d->workspace || sg_aligned16(d->workspace), "sg_conv3x3: workspace alignment");
-    SG_REQUIRE((int64_t)d->B * (d->H + 2) * (d->W + 2) * d->ldx < (1ll << 32) && (int64_t)d->Cout * 9 * d->Cin < (1ll << 32),
-               "sg_conv3x3: operands larger than 2^32 elements are not supported (32-bit DMA offsets)");
     SG_REQUIRE((int64_t)(d->W + 2) * d->ldx < (1 << 24), "sg_conv3x3: input row pitch must be below 2^24 elements");
+    {
+        // 32-bit LDS-DMA byte offsets (see gemm_params): the last byte of x — of the bordered [B, H+2, W+2] buffer with x_padded — and of
+        // w lies below 4 GiB from its base pointer.  (pixels <= 2^31 is checked first: the products below then stay inside 64 bits.)
+        const long long lim = 1ll << 31;
+        const int bord = d->x_padded ? 2 : 0;
+        const long long rows = (long long)d->B * (d->H + bord), pixels = rows <= lim ? rows * (d->W + bord) : lim + 1;
+        const long long x_span = pixels <= lim ? (pixels - 1) * (long long)d->ldx + d->Cin : lim + 1;
+        const long long w_span = (long long)d->Cout * 9 * d->Cin;
+        SG_REQUIRE(x_span <= lim,
+                   "sg_conv3x3: input x spans %s%lld elements ((pixels - 1) * ldx + Cin%s); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)",
+                   pixels <= lim ? "" : "more than ", x_span, d->x_padded ? ", zero border included" : "");
+        SG_REQUIRE(w_span <= lim,
+                   "sg_conv3x3: weights w span %lld elements (Cout * 9 * Cin); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)", w_span);
+    }
     SG_REQUIRE(9 * (d->Cin / 64) < 3000, "sg_conv3x3: Cin (%d) too large for the slab decode (kt / 9 by multiply-shift, kt < 3000)", d->Cin);
     const int hin = d->H << d->upsample2x, win = d->W << d->upsample2x;
     const int Ho = (hin + 2 - 3) / d->stride + 1, Wo = (win + 2 - 3) / d->stride + 1;

@@ -364,6 +364,13 @@ def gemm_stats_rows(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, **kw) -
     return rc
 
 
+def gemm_launch_plan(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, **kw) -> tuple:
+    """The decomposition a gemm() call with these arguments will use (sg_gemm_launch_plan; no launch): (tile rows, tile columns, K slices,
+    workgroups, threads per workgroup, kernel family: 0 register-staged, 1 LDS-DMA pipeline, 2 fat waves, 16 + ring depth latency kernel)."""
+    d, _, _ = _gemm_desc(a, w, out, **kw)
+    return tuple(_plan_of(lib.sg_gemm_launch_plan, d))
+
+
 def gemm_pair(first: tuple, second: tuple) -> None:
     """Two independent GEMMs in one launch (sg_gemm_pair_f16).  Each argument is ((a, w, out), {keywords of gemm()}); the
     outputs must not overlap and the two workspaces, if given, must be different buffers."""
@@ -460,6 +467,12 @@ def conv3x3_planned_splits(x: torch.Tensor, w_krsc: torch.Tensor, out: torch.Ten
     if rc < 0:
         check(rc, "sg_conv3x3_planned_splits")
     return rc
+
+
+def conv3x3_launch_plan(x: torch.Tensor, w_krsc: torch.Tensor, out: torch.Tensor, **kw) -> tuple:
+    """The decomposition a conv3x3() call with these arguments will use (sg_conv3x3_launch_plan; no launch): as gemm_launch_plan."""
+    d, _, _ = _conv_desc(x, w_krsc, out, **kw)
+    return tuple(_plan_of(lib.sg_conv3x3_launch_plan, d))
 
 
 def conv3x3_stats_rows(x: torch.Tensor, w_krsc: torch.Tensor, out: torch.Tensor, **kw) -> int:

@@ -129,6 +129,52 @@ def test_host_validation_rejects_before_launch(lib):
     assert lib.sg_gemm_workspace_bytes(128, 256, 1) == 0
 
 
+def test_forced_split_plans_and_operand_bound_on_the_host(lib):
+    """Host-only plan queries (nothing is launched).  A forced split_k is honoured as given on both candidate lists — also values the
+    cost model never enumerates for itself (7, 9, 11, 13, ...) — and clamped to the number of 64-deep K slabs; it never changes the tile:
+    the register-staged kernel (K % 64 != 0, unpadded convolution) keeps its one 128x128 tile, a development tile is kept on the
+    pipeline.  Operands must end within 2^31 elements (4 GiB of fp16) of their base: the LDS-DMA offsets are 32-bit byte offsets."""
+    from storygen_amd._lib import ConvDesc, GemmDesc
+    out = (C.c_int32 * 6)()
+
+    def gemm(M, N, K, split, lda=0, ldw=0):
+        d = GemmDesc()
+        d.A, d.W, d.C, d.workspace, d.workspace_bytes = 0x10000, 0x20000, 0x30000, 0x40000, M * N * 4 * 64
+        d.M, d.N, d.K, d.lda, d.ldw, d.ldc, d.split_k = M, N, K, lda or K, ldw or K, N, split
+        return lib.sg_gemm_launch_plan(C.byref(d), out), list(out)
+
+    def conv(H, ldx, padded, split):
+        d = ConvDesc()
+        d.x, d.w, d.y, d.workspace, d.workspace_bytes = 0x10000, 0x20000, 0x30000, 0x40000, 1 << 30
+        d.B, d.H, d.W, d.Cin, d.Cout, d.ldx, d.ldy, d.stride, d.x_padded, d.split_k = 1, H, 2, 64, 64, ldx, 64, 1, padded, split
+        return lib.sg_conv3x3_launch_plan(C.byref(d), out), list(out)
+
+    for split in list(range(1, 17)) + [24, 64]:
+        for M, N, K in ((100, 72, 136), (64, 64, 72)):                  # generic: 3 and 2 slabs
+            rc, plan = gemm(M, N, K, split)
+            assert rc == 0 and plan[:3] == [128, 128, min(split, -(-K // 64))] and plan[5] == 0, (M, N, K, split, plan)
+        rc, plan = conv(12, 64, 0, split)                                # unpadded convolution: generic, 9 slabs
+        assert rc == 0 and plan[:3] == [128, 128, min(split, 9)] and plan[5] == 0, (split, plan)
+        for bm, bn in ((256, 128), (128, 128), (256, 64), (128, 64), (64, 128), (64, 64)):
+            lib.sg_debug_set_tile(bm, bn, 0)
+            try:
+                rc, plan = gemm(100, 72, 640, split)
+                rc2, plan2 = conv(12, 64, 1, split)
+            finally:
+                lib.sg_debug_set_tile(0, 0, 0)
+            assert rc == 0 and plan[:3] == [bm, bn, min(split, 10)] and plan[5] == 1, (bm, bn, split, plan)
+            assert rc2 == 0 and plan2[:3] == [bm, bn, min(split, 9)] and plan2[5] == 1, (bm, bn, split, plan2)
+    assert gemm(64, 64, 64, 65)[0] == -1 and b"split_k" in lib.sg_last_error() and b"[0, 64]" in lib.sg_last_error()
+    # (M - 1) lda + K <= 2^31: M = 32768 rows of pitch 65536 end 128 KiB below 4 GiB; row 32768 would wrap to row 0
+    assert gemm(32768, 64, 64, 1, lda=65536)[0] == 0
+    assert gemm(32769, 64, 64, 1, lda=65536)[0] == -1 and b"operand A" in lib.sg_last_error() and b"2^31" in lib.sg_last_error()
+    assert gemm(64, 32768, 64, 1, ldw=65536)[0] == 0
+    assert gemm(64, 32776, 64, 1, ldw=65536)[0] == -1 and b"operand W" in lib.sg_last_error() and b"2^31" in lib.sg_last_error()
+    for padded, h_in, h_out in ((1, 126, 127), (0, 256, 257)):           # 512 pixels of pitch 2^22 - 8 end inside, the next row does not
+        assert conv(h_in, 2 ** 22 - 8, padded, 1)[0] == 0
+        assert conv(h_out, 2 ** 22 - 8, padded, 1)[0] == -1 and b"input x" in lib.sg_last_error() and b"2^31" in lib.sg_last_error()
+
+
 def test_backward_entry_points_validate_on_the_host(lib):
     """Same for the backward-pass entry points (BASELINE config 4): bad descriptors are refused before any launch."""
     from storygen_amd._lib import AttnBwdDesc, AttnDesc, GroupNormBwdDesc
