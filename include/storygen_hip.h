@@ -213,12 +213,17 @@ int sg_conv3x3_stats_tile_rows(const sg_conv3x3_desc* d);
  * and the development options).  No launch happens.  < 0 on an invalid descriptor. */
 int sg_conv3x3_planned_splits(const sg_conv3x3_desc* d);
 /* The decomposition a launch with this descriptor will use (host-only, nothing is launched): out[6] = {tile rows, tile columns,
- * K slices, workgroups, threads per workgroup, 1 if the LDS-DMA kernel applies else 0}.  For measurement tooling: a profiler
+ * K slices, workgroups, threads per workgroup, kernel family: 0 register-staged, 1 LDS-DMA pipeline of 64x64 per wave, 2 128x64 per
+ * wave, 16 + ring depth the 32x32-per-wave kernel}.  For measurement tooling: a profiler
  * reports (kernel instantiation, grid size) classes, this tells which problems fall into which (tools/traffic_from_pmc.py puts
  * the ALGORITHMIC bytes per launch next to the measured HBM bytes of every class).  No reference counterpart (the reference
  * calls cuDNN / cuBLAS through torch and never sees a launch geometry). */
 int sg_gemm_launch_plan(const sg_gemm_desc* d, int32_t* out);
 int sg_conv3x3_launch_plan(const sg_conv3x3_desc* d, int32_t* out);
+/* The same for sg_gemm_pair_f16(d0, d1) (host-only, nothing is launched): out[14] = {1 if one launch serves both problems else 0,
+ * the six integers of problem 0, the six integers of problem 1 — each as it is launched: on problem 0's tile when the launch is
+ * shared, on its own plan otherwise —, workgroups of the shared launch (the larger of the two grids rounded up to 8, times 2) or 0}. */
+int sg_gemm_pair_launch_plan(const sg_gemm_desc* d0, const sg_gemm_desc* d1, int32_t* out);
 
 /* conv_in: x fp32 NCHW [B, Cin<=8, H, W] -> y NHWC [B,H,W,Cout] (fp16, or fp32 when y_f32), 3x3 pad 1
  * (unet_2d_condition.py:124,411).

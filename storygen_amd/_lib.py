@@ -165,6 +165,7 @@ SIGNATURES = {
     "sg_conv3x3_planned_splits": (C.c_int, [C.POINTER(ConvDesc)]),
     "sg_gemm_launch_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(C.c_int32)]),
     "sg_conv3x3_launch_plan": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),
+    "sg_gemm_pair_launch_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), C.POINTER(C.c_int32)]),
     "sg_groupnorm_uses_pstats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "sg_groupnorm_is_fused": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "sg_ff_fused_pack_bytes": (C.c_size_t, [C.c_int32]),

@@ -1557,14 +1557,33 @@ int reduce_stats_rows(const MmaParams& p) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-struct Plan { int bm, bn, splits; int lat; int fat = 0; };      // lat: 0 = 64x64 per wave; else the 32x32-per-wave kernel (mma_lat_kernel) and its ring depth
+// Kernel family of a plan, also the sixth integer of sg_*_launch_plan: register-staged (mma_kernel, one 128x128 tile), LDS-DMA ring of
+// 64x64 per wave (mma_pipe_kernel), 128x64 per wave (mma_fat_kernel), FAM_LAT + ring depth: 32x32 per wave (mma_lat_kernel)
+enum { FAM_GENERIC = 0, FAM_PIPE = 1, FAM_FAT = 2, FAM_LAT = 16 };
 
-// Development options: storygen_amd/csrc/common.h SgOptions (set through sg_debug_set_option; never from the environment).
-struct TuneView {
-    SgOptions& o = sg_options();
-    int& bm = o.tile_m; int& bn = o.tile_n; int& no_pipe = o.no_pipe; int& no_split = o.no_split; int& no_nmajor = o.no_nmajor;
+// What a caller asks of the planner, beside the problem itself (MmaParams).
+struct TileHint { int bm = 0, bn = 0, waves = 0; };      // sg_gemm_desc.tile_m / tile_n / tile_waves
+struct PlanRequest {
+    int force_split = 0;                        // sg_gemm_desc.split_k
+    TileHint hint;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    const char* name = "";                      // the entry point, for error texts
+    bool in_pair = false;                       // a problem of sg_gemm_pair_f16 (development option lat_mask)
+    bool stats_optional = false;                // sg_*_stats_tile_rows: a plan that cannot deliver statistics drops them instead of failing
+    unsigned long long* prof = nullptr;         // sg_debug_*_anatomy
 };
-static const TuneView g_tune;
+
+// The launch of one problem: everything launch_plan / launch_pair_plan need beside MmaParams.
+struct Plan {
+    int bm = 0, bn = 0, splits = 1;
+    int family = FAM_GENERIC;
+    int threads = 0, grid = 0;                  // per workgroup; workgroups
+    int stats_rows = 0;                         // rows per statistics partial, 0 = the launch emits none
+    bool lat() const { return family >= FAM_LAT; }
+    int ring() const { return family - FAM_LAT; }
+};
+
 
 // Cost model (cycles at ~2.4 GHz).  Measured on MI355X (tools/bench_gemm.py): a CU pulls operand slabs from L2 into
 // LDS at ~18.5 B/cycle however many waves ask (L1 miss-level parallelism x L2 latency), so a launch is bound by
@@ -1576,25 +1595,26 @@ Plan choose_plan(int M, int N, int KT, int force_split, int max_ws_split, bool p
     static const int cand_pipe[6][2] = {{256, 128}, {128, 128}, {256, 64}, {128, 64}, {64, 128}, {64, 64}};
     static const int cand_gen[1][2] = {{128, 128}};      // the register-staged kernel is a cold path: one tile shape
     static const int split_opts[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16};
-    const int ncand = pipe ? 6 : 1;
+    const SgOptions& o = sg_options();
+    const int ncand = pipe ? 6 : 1, family = pipe ? FAM_PIPE : FAM_GENERIC;
     const double CUS = 256.0, BW = pipe ? 18.5 : 12.0;
     // A forced split (sg_gemm_desc.split_k > 1) is honoured as given on both candidate lists — any value of [2, 64], not only those the
     // cost model enumerates for itself — and clamped to the number of K slabs.  Slice z owns slabs [z, z + 1) * ceil(KT / s): where
     // ceil(KT / s) * (s - 1) >= KT the last slices own none and write zero partial tiles (the mainloops' `nt > 0` / `kt0 < kt1` guards).
     const int forced = force_split > 0 ? (force_split > KT ? KT : force_split) : 0;
     const int gen_bm = cand_gen[0][0], gen_bn = cand_gen[0][1];
-    Plan best{pipe ? 64 : gen_bm, pipe ? 64 : gen_bn, forced ? forced : 1, 0};
+    Plan best{pipe ? 64 : gen_bm, pipe ? 64 : gen_bn, forced ? forced : 1, family};
     double best_cost = 1e300;
     for (int ci = 0; ci < ncand; ++ci) {
         const int bm = pipe ? cand_pipe[ci][0] : cand_gen[ci][0], bn = pipe ? cand_pipe[ci][1] : cand_gen[ci][1];
-        if (pipe && g_tune.bm && (bm != g_tune.bm || bn != g_tune.bn)) continue;
-        if (pipe && !g_tune.bm && hint_bm && (bm != hint_bm || bn != hint_bn)) continue;
+        if (pipe && o.tile_m && (bm != o.tile_m || bn != o.tile_n)) continue;
+        if (pipe && !o.tile_m && hint_bm && (bm != hint_bm || bn != hint_bn)) continue;
         const long tiles = (long)sg_cdiv(M, bm) * sg_cdiv(N, bn);
         const double waves_per_block = pipe ? (bm / 64) * (bn / 64) : 4.0;
         const double mfma_per_slab = pipe ? 512.0 : 512.0 * (bm / 64.0) * (bn / 64.0) / 4.0;
         for (int s : split_opts) {
             if (forced) s = forced;
-            else if (s > 1 && (s > max_ws_split || KT / s < 2 || g_tune.no_split)) continue;
+            else if (s > 1 && (s > max_ws_split || KT / s < 2 || o.no_split)) continue;
             if (s > KT) continue;
             const double blocks = (double)tiles * s;
             const double slabs = sg_cdiv(KT, s);
@@ -1604,7 +1624,7 @@ Plan choose_plan(int M, int N, int KT, int force_split, int max_ws_split, bool p
             const double t_mfma = waves_per_simd * slabs * mfma_per_slab;
             double cost = (t_bw > t_mfma ? t_bw : t_mfma) + 2500.0 + blocks_per_cu * (bm * bn / 16.0);
             if (s > 1) cost += 5000.0 + (double)M * N * 4.0 * (s + 1) / 1500.0;   // second launch + partial tiles
-            if (cost < best_cost) { best_cost = cost; best = Plan{bm, bn, s, 0}; }
+            if (cost < best_cost) { best_cost = cost; best = Plan{bm, bn, s, family}; }
             if (forced) break;
         }
     }
@@ -1612,9 +1632,179 @@ Plan choose_plan(int M, int N, int KT, int force_split, int max_ws_split, bool p
     return best;
 }
 
+// GroupNorm statistics from the epilogue (MmaParams::stats) need whole tiles inside one image and the linear epilogue; a split-K
+// launch emits them from its second pass.  A launch that was asked for them but cannot deliver fails (the caller asks
+// sg_*_stats_tile_rows first, which plans with PlanRequest::stats_optional: the plan then drops them).  Sets pl.stats_rows.
+int check_stats(MmaParams& p, Plan& pl, const PlanRequest& rq) {
+    pl.stats_rows = 0;
+    if (!p.stats) return SG_OK;
+    // fused epilogue: one partial per row tile of the launch; split-K: from the second pass (reduce_stats_rows)
+    const int rows = p.splits == 1 ? pl.bm : reduce_stats_rows(p);
+    const bool ok = p.mode == SG_EPI_LINEAR && rows > 0 && p.stats_batch_rows > 0 && p.stats_batch_rows % rows == 0 &&
+                    p.M % p.stats_batch_rows == 0;
+    if (ok) { pl.stats_rows = rows; return SG_OK; }
+    if (rq.stats_optional) { p.stats = nullptr; return SG_OK; }
+    return sg_set_error(SG_EINVAL, "%s: epilogue statistics need the linear epilogue, a %d-row tile that divides the %d rows of an image "
+                        "and, under split-K (here %d), N %% 64 == 0: query sg_*_stats_tile_rows first", rq.name, rows, p.stats_batch_rows,
+                        p.splits);
+}
+
+// The 32x32-per-wave kernels (mma_lat_kernel): for launches that are a short dependent chain rather than a volume of FLOPs.
+//   64x64 tile, four waves, 4-stage ring: GEMMs of <= lat_tiles tiles and lat_min_kt .. lat_max_kt K slabs (development options);
+//   64x128 tile, eight waves, 6-stage ring (80 KB of WEIGHTS in flight per workgroup): M <= 256 — the 8x8 level, where a launch is its
+//   weight stream (29.5 MB for a 1280 -> 1280 convolution against 0.5 MB of activations) and what bounds it is the bytes a CU keeps in
+//   flight (the 64x64-per-wave tiles: 16 - 32 KB).
+// hint.waves = 4 with a 64x64 hint / 8 with 64x128: the caller asks for one; -1: never; 0: by size.  Fills pl (tile, K slices, ring
+// depth) and returns true, or returns false when the launch stays on the 64x64-per-wave kernels.
+template <bool CONV>
+bool lat_plan(const MmaParams& p, bool pipe, int force_split, int max_ws_split, TileHint hint, bool in_pair, Plan& pl) {
+    const SgOptions& o = sg_options();
+    if (!pipe || p.mode != SG_EPI_LINEAR || p.prof || hint.waves < 0 || o.tile_m) return false;
+    // development option lat_mask (bisecting): which launch kinds may take the kernel by size — 1 paired launches, 2 LayerNorm-folded
+    // consumers, 4 GroupNorm partials, 8 K slices, 16 LayerNorm-partial producers, 32 everything else
+    if (hint.waves == 0) {
+        // (the columns-are-tokens fold, ln_mode 2, only ever occurs as the second problem of a pair: it shares the pairs' bit)
+        const int kind = (in_pair || p.ln_mode == 2) ? 1 : p.ln_mode ? 2 : p.stats ? 4 : p.ln_out ? 16 : 32;
+        if (!(o.lat_mask & kind)) return false;
+    }
+    const bool hinted = hint.bm != 0 || hint.bn != 0 || hint.waves != 0;
+    const bool ask_sq = hint.bm == 64 && hint.bn == 64 && hint.waves == 4, ask_wide = hint.bm == 64 && hint.bn == 128 && hint.waves == 8;
+    if (hinted && !ask_sq && !ask_wide) return false;
+    const long tiles_sq = (long)sg_cdiv(p.M, 64) * sg_cdiv(p.N, 64), tiles_wide = (long)sg_cdiv(p.M, 64) * sg_cdiv(p.N, 128);
+    const bool wide = ask_wide || (!hinted && o.lat_wide && p.M <= o.lat_wide_m && p.N >= 256 && p.KT >= 40);
+    const bool sq = !wide && (ask_sq || (!hinted && !CONV && tiles_sq <= o.lat_tiles && p.KT >= o.lat_min_kt &&
+                                         (p.KT <= o.lat_max_kt || tiles_sq <= 128)));
+    if (!wide && !sq) return false;
+    const long tiles = wide ? tiles_wide : tiles_sq;
+    // K slices only where the tiles alone leave most CUs idle (M <= 256 at N = 1280): enough for ~256 workgroups, >= min_slabs each
+    const int min_slabs = wide ? 8 : 16;
+    int sp = 1;
+    if (force_split > 0) sp = force_split > p.KT ? p.KT : force_split;
+    else if (tiles <= 128 && !o.no_split && (o.lat_mask & 8)) {
+        sp = (int)(256 / tiles);
+        if (sp > p.KT / min_slabs) sp = p.KT / min_slabs;
+        if (sp > max_ws_split) sp = max_ws_split;
+        if (sp > MAX_AUTO_SPLIT) sp = MAX_AUTO_SPLIT;
+        if (sp < 1) sp = 1;
+    }
+    // 64x64: 4 stages (three slabs = 48 KB in flight per workgroup, two workgroups per CU) measured equal or better than 8 on every
+    // main-pass shape, incl. those of <= 256 workgroups (M768 N1280 K1280: 9.9 vs 10.7 us per graph node — the 8-stage prologue issues
+    // 28 DMA pieces per wave before the first slab can land; profiles/r06b_*); 8 stays behind the development option
+    pl = Plan{64, wide ? 128 : 64, sp, FAM_LAT + (wide ? 6 : (o.lat_stages == 8 ? 8 : 4))};
+    return true;
+}
+
+// Development option big_m (common.h): launches of M >= big_m rows without a tile hint take the (big_bm, big_bn) tile.
+TileHint apply_big_m(TileHint hint, int M, bool pipe) {
+    const SgOptions& o = sg_options();
+    if (o.big_m > 0 && M >= o.big_m && hint.bm == 0 && hint.bn == 0 && hint.waves == 0 && pipe) { hint.bm = o.big_bm; hint.bn = o.big_bn; }
+    return hint;
+}
+
+bool asks_fat(TileHint h) { return h.waves == 8 && ((h.bm == 512 && h.bn == 128) || (h.bm == 256 && h.bn == 256)); }
+bool asks_lat(TileHint h) { return (h.waves == 4 && h.bm == 64 && h.bn == 64) || (h.waves == 8 && h.bm == 64 && h.bn == 128); }
+
+// Tile shape, K slices and kernel family: the 128x64-per-wave tiles by hint or option, else the 32x32-per-wave kernels where
+// lat_plan takes the launch, else the cost model.  A hint that asks for a family which does not apply is dropped there.
+template <bool CONV>
+Plan choose_family(const MmaParams& p, const PlanRequest& rq, TileHint hint, bool pipe, int max_ws_split) {
+    const SgOptions& o = sg_options();
+    const bool fat_ok = pipe && !p.prof && !o.tile_m && rq.force_split <= 1 && (p.mode == SG_EPI_LINEAR || p.mode == SG_EPI_GEGLU);
+    if (asks_fat(hint)) {
+        if (fat_ok) return Plan{hint.bm, hint.bn, 1, FAM_FAT};
+        hint = TileHint{};                                                                  // asked for, not applicable: as without a hint
+    }
+    // development option fat_m: large convolutions without a hint take 512x128 where an image's rows divide by 512 (GroupNorm partials are
+    // per row tile)
+    else if (CONV && fat_ok && o.fat_m > 0 && p.M >= o.fat_m && hint.bm == 0 && hint.bn == 0 && hint.waves == 0) {
+        // (256x256 lost to 512x128 on every shape measured, profiles/r06bi_*: by hint only)
+        const int rows = p.stats ? p.stats_batch_rows : 512;
+        if (rows % 512 == 0) return Plan{512, 128, 1, FAM_FAT};
+    }
+    Plan pl;
+    if (lat_plan<CONV>(p, pipe, rq.force_split, max_ws_split, hint, rq.in_pair, pl)) return pl;
+    if (asks_lat(hint)) hint.bm = hint.bn = 0;                                              // asked for, not applicable: the cost model decides
+    return choose_plan(p.M, p.N, p.KT, rq.force_split, max_ws_split, pipe, hint.bm, hint.bn);
+}
+
+// Each XCD has a private L2 and consecutive tile ids share one (xcd_remap): let them share the LARGER operand panel, so
+// that it is fetched from HBM / Infinity Cache by one XCD instead of by all that own a tile of it.  At the 16x16 and
+// 8x8 latent levels the weights (up to 59 MB per layer) dwarf the activations: walk M first there.
+// group_m: the number of row tiles a wave of ~32 / splits consecutive tiles spans (tile_of_id).  Bytes that wave asks its L2 for =
+// gm activation panels + (wave / gm) weight panels; pick the gm in {1, 2, 4, 8, 16, all} with the fewest (ties: the larger gm, i.e.
+// the former M-first walk).  Development option no_nmajor = 1: N first everywhere (group_m = 1).
+template <bool CONV>
+int choose_group_m(const MmaParams& p, int splits) {
+    const double a_bytes = CONV ? 2.0 * p.M * (p.K / 9) * (p.stride == 1 && !p.ups ? 1.0 : (p.ups ? 0.25 : 4.0)) : 2.0 * p.M * p.K;
+    const double w_bytes = 2.0 * p.N * p.K;
+    const double a_panel = a_bytes / p.tiles_m, w_panel = w_bytes / p.tiles_n;
+    const int wave_tiles = splits >= 32 ? 1 : 32 / splits;
+    int best = 1;
+    double best_bytes = 1e300;
+    const int cands[6] = {1, 2, 4, 8, 16, p.tiles_m};
+    for (int c : cands) {
+        const int gm = c < p.tiles_m ? c : p.tiles_m;
+        const int width = gm * p.tiles_n;
+        int rows, cols;
+        if (width >= wave_tiles) {                     // the wave lies inside one group: gm rows x wave / gm columns
+            rows = gm < wave_tiles ? gm : wave_tiles;
+            cols = (wave_tiles + rows - 1) / rows;
+        } else {                                       // it spans several whole groups: all columns, gm rows per group
+            rows = gm * ((wave_tiles + width - 1) / width);
+            if (rows > p.tiles_m) rows = p.tiles_m;
+            cols = p.tiles_n;
+        }
+        const double bytes = rows * a_panel + cols * w_panel;
+        if (bytes <= best_bytes) { best_bytes = bytes; best = gm; }
+    }
+    return sg_options().no_nmajor ? 1 : best;
+}
+
+// The multiply-shift divisors of the kernels' prologues, from the decomposition fields.
+template <bool CONV>
+void fill_fastdiv(MmaParams& p) {
+    p.fd_splits = make_fastdiv((unsigned)p.splits);
+    p.fd_group_w = make_fastdiv((unsigned)(p.group_m * p.tiles_n));
+    p.fd_group_m = make_fastdiv((unsigned)p.group_m);
+    p.fd_rpb = make_fastdiv((unsigned)(p.rows_per_batch > 0 ? p.rows_per_batch : 1));
+    if (CONV) {
+        p.fd_hw = make_fastdiv((unsigned)(p.Ho * p.Wo));
+        p.fd_wo = make_fastdiv((unsigned)p.Wo);
+        p.fd_cpt = make_fastdiv((unsigned)p.cpt);
+    }
+}
+
+int threads_of(const Plan& pl) {
+    return pl.family == FAM_FAT ? 512 : pl.lat() ? 64 * (pl.bm / 32) * (pl.bn / 32) : pl.family == FAM_PIPE ? 64 * (pl.bm / 64) * (pl.bn / 64) : 256;
+}
+
+// Plans one problem: pl = the launch, and the decomposition fields of p (K slices, tile counts, tile order, divisors).  The LDS-DMA
+// kernels apply where no load needs a predicate (K % 64 == 0; conv input zero-bordered), else the register-staged kernel.
+template <bool CONV>
+int plan_mma(MmaParams& p, const PlanRequest& rq, Plan& pl) {
+    p.KT = sg_cdiv(p.K, BK);
+    p.prof = rq.prof;
+    const bool pipe = (p.K % BK == 0) && (!CONV || p.padded) && !sg_options().no_pipe;
+    const size_t per_split = (size_t)p.M * p.N * 4;
+    const int max_ws_split = rq.ws ? (int)(rq.ws_bytes / per_split > 64 ? 64 : rq.ws_bytes / per_split) : 1;
+    pl = choose_family<CONV>(p, rq, apply_big_m(rq.hint, p.M, pipe), pipe, max_ws_split);
+    if (pl.splits > 1 && (rq.ws == nullptr || rq.ws_bytes < per_split * pl.splits))
+        return sg_set_error(SG_EINVAL, "%s: split_k=%d needs %zu workspace bytes, got %zu", rq.name, pl.splits, per_split * pl.splits,
+                            rq.ws_bytes);
+    p.ws = reinterpret_cast<float*>(rq.ws);
+    p.splits = pl.splits;
+    p.kt_per_split = sg_cdiv(p.KT, pl.splits);
+    p.tiles_m = sg_cdiv(p.M, pl.bm);
+    p.tiles_n = sg_cdiv(p.N, pl.bn);
+    p.group_m = choose_group_m<CONV>(p, pl.splits);
+    fill_fastdiv<CONV>(p);
+    pl.threads = threads_of(pl);
+    pl.grid = p.tiles_m * p.tiles_n * pl.splits;
+    return check_stats(p, pl, rq);
+}
+
 template <int WGM, int WGN, bool CONV>
-void launch_pipe(const MmaParams& p, dim3 grid, hipStream_t st) {
-    const dim3 block(64 * WGM * WGN);
+void launch_pipe(const MmaParams& p, dim3 grid, dim3 block, hipStream_t st) {
 #ifdef SG_BUILD_EXPERIMENTS
     if (p.prof) {
         hipLaunchKernelGGL((mma_pipe_prof_kernel<WGM, WGN, CONV>), grid, block, 0, st, p);
@@ -1629,162 +1819,6 @@ void launch_pipe(const MmaParams& p, dim3 grid, hipStream_t st) {
         }
     }
     hipLaunchKernelGGL((mma_pipe_kernel<WGM, WGN, CONV>), grid, block, 0, st, p);
-}
-
-thread_local unsigned long long* g_prof = nullptr;     // set by sg_debug_*_anatomy around one launch
-thread_local int g_query_rows = 0;                     // result of a stats query (rows per partial = the tile height), 0 = none
-thread_local bool g_stats_query = false;               // sg_*_stats_tile_rows: plan only, report eligibility instead of failing
-thread_local bool g_plan_query = false;                // sg_conv3x3_planned_splits: plan only, report the number of K slices
-thread_local int32_t* g_plan_out = nullptr;            // sg_*_launch_plan: also {tile rows, tile columns, K slices, workgroups, threads per workgroup, pipelined}
-
-// GroupNorm statistics from the epilogue (MmaParams::stats) need whole tiles inside one image and the linear epilogue; a split-K
-// launch emits them from its second pass.  A launch that was asked for them but cannot deliver fails (the caller asks
-// sg_*_stats_tile_rows first).
-int check_stats(MmaParams& p, int bm, const char* name) {
-    if (!p.stats) return SG_OK;
-    // fused epilogue: one partial per row tile of the launch; split-K: from the second pass (reduce_stats_rows)
-    const int rows = p.splits == 1 ? bm : reduce_stats_rows(p);
-    const bool ok = p.mode == SG_EPI_LINEAR && rows > 0 && p.stats_batch_rows > 0 && p.stats_batch_rows % rows == 0 &&
-                    p.M % p.stats_batch_rows == 0;
-    if (ok) return SG_OK;
-    if (g_stats_query) { p.stats = nullptr; return SG_OK; }
-    return sg_set_error(SG_EINVAL, "%s: epilogue statistics need the linear epilogue, a %d-row tile that divides the %d rows of an image "
-                        "and, under split-K (here %d), N %% 64 == 0: query sg_*_stats_tile_rows first", name, rows, p.stats_batch_rows,
-                        p.splits);
-}
-
-// Decomposition of one problem: tile shape, K split, tile order; fills the corresponding fields of p.  `pipe` = the LDS-DMA
-// kernel applies (no load needs a predicate: K % 64 == 0; conv input zero-bordered), else the register-staged kernel.
-// The 32x32-per-wave kernels (mma_lat_kernel): for launches that are a short dependent chain rather than a volume of FLOPs.
-//   64x64 tile, four waves, 4-stage ring: GEMMs of <= lat_tiles tiles and lat_min_kt .. lat_max_kt K slabs (development options);
-//   64x128 tile, eight waves, 6-stage ring (80 KB of WEIGHTS in flight per workgroup): M <= 256 — the 8x8 level, where a launch is its
-//   weight stream (29.5 MB for a 1280 -> 1280 convolution against 0.5 MB of activations) and what bounds it is the bytes a CU keeps in
-//   flight (the 64x64-per-wave tiles: 16 - 32 KB).
-// hint_waves = 4 with a 64x64 hint / 8 with 64x128: the caller asks for one; -1: never; 0: by size.  Fills pl (tile, K slices, ring
-// depth) and returns true, or returns false when the launch stays on the 64x64-per-wave kernels.
-thread_local bool g_in_pair = false;        // sg_gemm_pair_f16 is planning (development option lat_mask)
-
-template <bool CONV>
-bool lat_plan(const MmaParams& p, bool pipe, int force_split, int max_ws_split, int hint_bm, int hint_bn, int hint_waves, Plan& pl) {
-    if (!pipe || p.mode != SG_EPI_LINEAR || p.prof || hint_waves < 0 || g_tune.bm) return false;
-    const SgOptions& o = sg_options();
-    // development option lat_mask (bisecting): which launch kinds may take the kernel by size — 1 paired launches, 2 LayerNorm-folded
-    // consumers, 4 GroupNorm partials, 8 K slices, 16 LayerNorm-partial producers, 32 everything else
-    if (hint_waves == 0) {
-        // (the columns-are-tokens fold, ln_mode 2, only ever occurs as the second problem of a pair: it shares the pairs' bit)
-        const int kind = (g_in_pair || p.ln_mode == 2) ? 1 : p.ln_mode ? 2 : p.stats ? 4 : p.ln_out ? 16 : 32;
-        if (!(o.lat_mask & kind)) return false;
-    }
-    const bool hinted = hint_bm != 0 || hint_bn != 0 || hint_waves != 0;
-    const bool ask_sq = hint_bm == 64 && hint_bn == 64 && hint_waves == 4, ask_wide = hint_bm == 64 && hint_bn == 128 && hint_waves == 8;
-    if (hinted && !ask_sq && !ask_wide) return false;
-    const long tiles_sq = (long)sg_cdiv(p.M, 64) * sg_cdiv(p.N, 64), tiles_wide = (long)sg_cdiv(p.M, 64) * sg_cdiv(p.N, 128);
-    const bool wide = ask_wide || (!hinted && o.lat_wide && p.M <= o.lat_wide_m && p.N >= 256 && p.KT >= 40);
-    const bool sq = !wide && (ask_sq || (!hinted && !CONV && tiles_sq <= o.lat_tiles && p.KT >= o.lat_min_kt &&
-                                         (p.KT <= o.lat_max_kt || tiles_sq <= 128)));
-    if (!wide && !sq) return false;
-    const long tiles = wide ? tiles_wide : tiles_sq;
-    // K slices only where the tiles alone leave most CUs idle (M <= 256 at N = 1280): enough for ~256 workgroups, >= min_slabs each
-    const int min_slabs = wide ? 8 : 16;
-    int sp = 1;
-    if (force_split > 0) sp = force_split > p.KT ? p.KT : force_split;
-    else if (tiles <= 128 && !g_tune.no_split && (o.lat_mask & 8)) {
-        sp = (int)(256 / tiles);
-        if (sp > p.KT / min_slabs) sp = p.KT / min_slabs;
-        if (sp > max_ws_split) sp = max_ws_split;
-        if (sp > MAX_AUTO_SPLIT) sp = MAX_AUTO_SPLIT;
-        if (sp < 1) sp = 1;
-    }
-    // 64x64: 4 stages (three slabs = 48 KB in flight per workgroup, two workgroups per CU) measured equal or better than 8 on every
-    // main-pass shape, incl. those of <= 256 workgroups (M768 N1280 K1280: 9.9 vs 10.7 us per graph node — the 8-stage prologue issues
-    // 28 DMA pieces per wave before the first slab can land; profiles/r06b_*); 8 stays behind the development option
-    pl = Plan{64, wide ? 128 : 64, sp, wide ? 6 : (o.lat_stages == 8 ? 8 : 4)};
-    return true;
-}
-
-template <bool CONV>
-int plan_mma(MmaParams& p, int force_split, int hint_bm, int hint_bn, int hint_waves, void* ws, size_t ws_bytes, const char* name,
-             Plan& pl, bool& pipe) {
-    p.KT = sg_cdiv(p.K, BK);
-    p.prof = g_prof;
-    pipe = (p.K % BK == 0) && (!CONV || p.padded) && !g_tune.no_pipe;
-    const size_t per_split = (size_t)p.M * p.N * 4;
-    const int max_ws_split = ws ? (int)(ws_bytes / per_split > 64 ? 64 : ws_bytes / per_split) : 1;
-    if (sg_options().big_m > 0 && p.M >= sg_options().big_m && hint_bm == 0 && hint_bn == 0 && hint_waves == 0 && pipe) {
-        hint_bm = sg_options().big_bm; hint_bn = sg_options().big_bn;       // development option: see common.h
-    }
-    const bool ask_fat = hint_waves == 8 && ((hint_bm == 512 && hint_bn == 128) || (hint_bm == 256 && hint_bn == 256));
-    const bool fat_ok = pipe && !p.prof && !g_tune.bm && force_split <= 1 && (p.mode == SG_EPI_LINEAR || p.mode == SG_EPI_GEGLU);
-    // development option fat_m: large convolutions without a hint take 512x128 where an image's rows divide by 512 (GroupNorm partials are
-    // per row tile)
-    int auto_bm = 0, auto_bn = 0;
-    if (CONV && fat_ok && sg_options().fat_m > 0 && p.M >= sg_options().fat_m && hint_bm == 0 && hint_bn == 0 && hint_waves == 0) {
-        // (256x256 lost to 512x128 on every shape measured, profiles/r06bi_*: by hint only)
-        const int rows = p.stats ? p.stats_batch_rows : 512;
-        if (rows % 512 == 0) { auto_bm = 512; auto_bn = 128; }
-    }
-    if (ask_fat && fat_ok) {
-        pl = Plan{hint_bm, hint_bn, 1, 0, 1};
-    } else if (auto_bm) {
-        pl = Plan{auto_bm, auto_bn, 1, 0, 1};
-    } else if (!lat_plan<CONV>(p, pipe, force_split, max_ws_split, ask_fat ? 0 : hint_bm, ask_fat ? 0 : hint_bn, ask_fat ? 0 : hint_waves, pl)) {
-        if (ask_fat) hint_bm = hint_bn = 0;                                                 // asked for, not applicable: the cost model decides
-        if ((hint_waves == 4 && hint_bm == 64 && hint_bn == 64) || (hint_waves == 8 && hint_bm == 64 && hint_bn == 128))
-            hint_bm = hint_bn = 0;                                                          // asked for, not applicable: the cost model decides
-        pl = choose_plan(p.M, p.N, p.KT, force_split, max_ws_split, pipe, hint_bm, hint_bn);
-    }
-    if (pl.splits > 1) {
-        const size_t need = per_split * pl.splits;
-        if (ws == nullptr || ws_bytes < need)
-            return sg_set_error(SG_EINVAL, "%s: split_k=%d needs %zu workspace bytes, got %zu", name, pl.splits, need,
-                                ws_bytes);
-    }
-    p.ws = reinterpret_cast<float*>(ws);
-    p.splits = pl.splits;
-    p.kt_per_split = sg_cdiv(p.KT, pl.splits);
-    p.tiles_m = sg_cdiv(p.M, pl.bm);
-    p.tiles_n = sg_cdiv(p.N, pl.bn);
-    // Each XCD has a private L2 and consecutive tile ids share one (xcd_remap): let them share the LARGER operand panel, so
-    // that it is fetched from HBM / Infinity Cache by one XCD instead of by all that own a tile of it.  At the 16x16 and
-    // 8x8 latent levels the weights (up to 59 MB per layer) dwarf the activations: walk M first there.
-    const double a_bytes = CONV ? 2.0 * p.M * (p.K / 9) * (p.stride == 1 && !p.ups ? 1.0 : (p.ups ? 0.25 : 4.0)) : 2.0 * p.M * p.K;
-    const double w_bytes = 2.0 * p.N * p.K;
-    // group_m: the number of row tiles a wave of ~32 / splits consecutive tiles spans (tile_of_id).  Bytes that wave asks its L2 for =
-    // gm activation panels + (wave / gm) weight panels; pick the gm in {1, 2, 4, 8, 16, all} with the fewest (ties: the larger gm, i.e.
-    // the former M-first walk).  Development option no_nmajor = 1: N first everywhere (group_m = 1).
-    {
-        const double a_panel = a_bytes / p.tiles_m, w_panel = w_bytes / p.tiles_n;
-        const int wave_tiles = pl.splits >= 32 ? 1 : 32 / pl.splits;
-        int best = 1;
-        double best_bytes = 1e300;
-        const int cands[6] = {1, 2, 4, 8, 16, p.tiles_m};
-        for (int c : cands) {
-            const int gm = c < p.tiles_m ? c : p.tiles_m;
-            const int width = gm * p.tiles_n;
-            int rows, cols;
-            if (width >= wave_tiles) {                     // the wave lies inside one group: gm rows x wave / gm columns
-                rows = gm < wave_tiles ? gm : wave_tiles;
-                cols = (wave_tiles + rows - 1) / rows;
-            } else {                                       // it spans several whole groups: all columns, gm rows per group
-                rows = gm * ((wave_tiles + width - 1) / width);
-                if (rows > p.tiles_m) rows = p.tiles_m;
-                cols = p.tiles_n;
-            }
-            const double bytes = rows * a_panel + cols * w_panel;
-            if (bytes <= best_bytes) { best_bytes = bytes; best = gm; }
-        }
-        p.group_m = g_tune.no_nmajor ? 1 : best;
-    }
-    p.fd_splits = make_fastdiv((unsigned)p.splits);
-    p.fd_group_w = make_fastdiv((unsigned)(p.group_m * p.tiles_n));
-    p.fd_group_m = make_fastdiv((unsigned)p.group_m);
-    p.fd_rpb = make_fastdiv((unsigned)(p.rows_per_batch > 0 ? p.rows_per_batch : 1));
-    if (CONV) {
-        p.fd_hw = make_fastdiv((unsigned)(p.Ho * p.Wo));
-        p.fd_wo = make_fastdiv((unsigned)p.Wo);
-        p.fd_cpt = make_fastdiv((unsigned)p.cpt);
-    }
-    return check_stats(p, pl.bm, name);
 }
 
 int launch_reduce(const MmaParams& p, hipStream_t st) {
@@ -1805,43 +1839,27 @@ int launch_reduce(const MmaParams& p, hipStream_t st) {
     return SG_OK;
 }
 
+// Launches one planned problem (and the second pass of a split-K one): the one place that maps a plan to a kernel instantiation.
 template <bool CONV>
-int launch_mma(MmaParams& p, int force_split, int hint_bm, int hint_bn, int hint_waves, void* ws, size_t ws_bytes, hipStream_t st, const char* name) {
-    Plan pl;
-    bool pipe;
-    if (int rc = plan_mma<CONV>(p, force_split, hint_bm, hint_bn, hint_waves, ws, ws_bytes, name, pl, pipe)) return rc;
-    if (g_stats_query) {
-        g_query_rows = p.stats ? (pl.splits > 1 ? reduce_stats_rows(p) : pl.bm) : 0;
-        return SG_OK;
-    }
-    if (g_plan_query) {
-        g_query_rows = pl.splits;
-        if (g_plan_out) {
-            g_plan_out[0] = pl.bm; g_plan_out[1] = pl.bn; g_plan_out[2] = pl.splits; g_plan_out[3] = p.tiles_m * p.tiles_n * pl.splits;
-            g_plan_out[4] = pl.fat ? 512 : pl.lat ? 64 * (pl.bm / 32) * (pl.bn / 32) : pipe ? 64 * (pl.bm / 64) * (pl.bn / 64) : 256;
-            g_plan_out[5] = pl.fat ? 2 : pl.lat ? 16 + pl.lat : pipe ? 1 : 0;        // 2: 128x64 per wave; 16 + ring depth: the 32x32-per-wave kernel
-        }
-        return SG_OK;
-    }
+int launch_plan(const MmaParams& p, const Plan& pl, hipStream_t st, const char* name) {
     if (p.defer && pl.splits <= 1)
         return sg_set_error(SG_EINVAL, "%s: defer_reduce needs a split-K launch (query sg_conv3x3_planned_splits first)", name);
-    dim3 grid(p.tiles_m * p.tiles_n * pl.splits);
-    if (pl.fat) {
-        if (pl.bm == 512) hipLaunchKernelGGL((mma_fat_kernel<4, 2, CONV>), grid, dim3(512), 0, st, p);
-        else hipLaunchKernelGGL((mma_fat_kernel<2, 4, CONV>), grid, dim3(512), 0, st, p);
-    } else if (pl.lat) {
-        if (pl.bn == 128) hipLaunchKernelGGL((mma_lat_kernel<2, 4, CONV, 6>), grid, dim3(512), 0, st, p);
-        else if (pl.lat == 8) hipLaunchKernelGGL((mma_lat_kernel<2, 2, CONV, 8>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((mma_lat_kernel<2, 2, CONV, 4>), grid, dim3(256), 0, st, p);
-    } else if (pipe) {
-        if (pl.bm == 256 && pl.bn == 128) launch_pipe<4, 2, CONV>(p, grid, st);
-        else if (pl.bm == 128 && pl.bn == 128) launch_pipe<2, 2, CONV>(p, grid, st);
-        else if (pl.bm == 256 && pl.bn == 64) launch_pipe<4, 1, CONV>(p, grid, st);
-        else if (pl.bm == 128 && pl.bn == 64) launch_pipe<2, 1, CONV>(p, grid, st);
-        else if (pl.bm == 64 && pl.bn == 128) launch_pipe<1, 2, CONV>(p, grid, st);
-        else launch_pipe<1, 1, CONV>(p, grid, st);
+    const dim3 grid(pl.grid), block(pl.threads);
+    if (pl.family == FAM_FAT) {
+        if (pl.bm == 512) hipLaunchKernelGGL((mma_fat_kernel<4, 2, CONV>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((mma_fat_kernel<2, 4, CONV>), grid, block, 0, st, p);
+    } else if (pl.lat()) {
+        if (pl.bn == 128) hipLaunchKernelGGL((mma_lat_kernel<2, 4, CONV, 6>), grid, block, 0, st, p);
+        else if (pl.ring() == 8) hipLaunchKernelGGL((mma_lat_kernel<2, 2, CONV, 8>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((mma_lat_kernel<2, 2, CONV, 4>), grid, block, 0, st, p);
+    } else if (pl.family == FAM_PIPE) {
+        if (pl.bm == 256 && pl.bn == 128) launch_pipe<4, 2, CONV>(p, grid, block, st);
+        else if (pl.bm == 128 && pl.bn == 128) launch_pipe<2, 2, CONV>(p, grid, block, st);
+        else if (pl.bm == 256 && pl.bn == 64) launch_pipe<4, 1, CONV>(p, grid, block, st);
+        else if (pl.bm == 128 && pl.bn == 64) launch_pipe<2, 1, CONV>(p, grid, block, st);
+        else if (pl.bm == 64 && pl.bn == 128) launch_pipe<1, 2, CONV>(p, grid, block, st);
+        else launch_pipe<1, 1, CONV>(p, grid, block, st);
     } else {
-        dim3 block(256);
         if (p.ln_mode) return sg_set_error(SG_EINVAL, "%s: a folded LayerNorm needs the LDS-DMA kernel (K %% 64 == 0)", name);
         if (pl.bm == 128 && pl.bn == 128) hipLaunchKernelGGL((mma_kernel<128, 128, CONV>), grid, block, 0, st, p);
         else return sg_set_error(SG_EINVAL, "%s: internal: the register-staged kernel has only the 128x128 tile", name);
@@ -1849,6 +1867,10 @@ int launch_mma(MmaParams& p, int force_split, int hint_bm, int hint_bn, int hint
     SG_CHECK_LAUNCH(name);
     if (p.defer) return SG_OK;          // the consumer sums the slices (sg_groupnorm_desc.split_ws)
     return launch_reduce(p, st);
+}
+
+void report_plan(const Plan& pl, int32_t* out) {
+    out[0] = pl.bm; out[1] = pl.bn; out[2] = pl.splits; out[3] = pl.grid; out[4] = pl.threads; out[5] = pl.family;
 }
 
 int check_out_res(const char* who, int flags, const void* C, int64_t ldc, const void* C2, int64_t ldc2, const void* res1,
@@ -1955,73 +1977,24 @@ int gemm_params(const sg_gemm_desc* d, MmaParams& p, const char* who) {
     return check_tile_hint(who, d->tile_m, d->tile_n, d->tile_waves);
 }
 
-template <int WGM, int WGN>
-void launch_pair(const MmaPair& pp, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((mma_pipe_pair_kernel<WGM, WGN>), grid, dim3(64 * WGM * WGN), 0, st, pp);
-}
-}  // namespace
-
-extern "C" int sg_gemm_f16(const sg_gemm_desc* d, sg_stream_t stream) {
-    MmaParams p;
-    if (int rc = gemm_params(d, p, "sg_gemm_f16")) return rc;
-    return launch_mma<false>(p, d->ln_mode ? 1 : d->split_k, d->tile_m, d->tile_n, d->tile_waves, d->workspace, d->workspace_bytes, (hipStream_t)stream, "sg_gemm_f16");
-}
-
-extern "C" int sg_gemm_pair_f16(const sg_gemm_desc* d0, const sg_gemm_desc* d1, sg_stream_t stream) {
-    MmaPair pp;
-    if (int rc = gemm_params(d0, pp.p0, "sg_gemm_pair_f16[0]")) return rc;
-    if (int rc = gemm_params(d1, pp.p1, "sg_gemm_pair_f16[1]")) return rc;
-    SG_REQUIRE(!(d0->workspace && d1->workspace) ||
-               (reinterpret_cast<char*>(d0->workspace) + d0->workspace_bytes <= reinterpret_cast<char*>(d1->workspace) ||
-                reinterpret_cast<char*>(d1->workspace) + d1->workspace_bytes <= reinterpret_cast<char*>(d0->workspace)),
-               "sg_gemm_pair_f16: the two problems run concurrently and need disjoint workspaces");
-    hipStream_t st = (hipStream_t)stream;
-    Plan pl0, pl1;
-    bool pipe0, pipe1;
-    const int sk0 = d0->ln_mode ? 1 : d0->split_k, sk1 = d1->ln_mode ? 1 : d1->split_k;
-    struct PairScope { PairScope() { g_in_pair = true; } ~PairScope() { g_in_pair = false; } } pair_scope;
-    if (int rc = plan_mma<false>(pp.p0, sk0, d0->tile_m, d0->tile_n, d0->tile_waves, d0->workspace, d0->workspace_bytes, "sg_gemm_pair_f16[0]", pl0, pipe0)) return rc;
-    // one kernel instantiation serves both problems: the second one is planned on the first one's tile shape (and kernel family)
-    if (int rc = plan_mma<false>(pp.p1, sk1, pl0.bm, pl0.bn, pl0.lat ? (pl0.bn == 128 ? 8 : 4) : -1, d1->workspace, d1->workspace_bytes, "sg_gemm_pair_f16[1]", pl1, pipe1)) return rc;
-    if (!pipe0 || !pipe1 || pl1.bm != pl0.bm || pl1.bn != pl0.bn || (pl0.lat != 0) != (pl1.lat != 0) || (pl0.lat && pl0.bn == 128)) {        // not pairable (K % 64, forced tile): two launches
-        if (int rc = launch_mma<false>(pp.p0, sk0, d0->tile_m, d0->tile_n, d0->tile_waves, d0->workspace, d0->workspace_bytes, st, "sg_gemm_pair_f16[0]")) return rc;
-        return launch_mma<false>(pp.p1, sk1, d1->tile_m, d1->tile_n, d1->tile_waves, d1->workspace, d1->workspace_bytes, st, "sg_gemm_pair_f16[1]");
-    }
-    const int g0 = pp.p0.tiles_m * pp.p0.tiles_n * pp.p0.splits, g1 = pp.p1.tiles_m * pp.p1.tiles_n * pp.p1.splits;
-    // grid.x is a multiple of 8 so that block (x, 1) sits on XCD x % 8 like block (x, 0): xcd_remap keeps its meaning
-    dim3 grid(((g0 > g1 ? g0 : g1) + 7) & ~7, 2);
-    if (pl0.lat) {
-        if (sg_options().lat_stages == 8) hipLaunchKernelGGL(mma_lat_pair_kernel<8>, grid, dim3(256), 0, st, pp);
-        else hipLaunchKernelGGL(mma_lat_pair_kernel<4>, grid, dim3(256), 0, st, pp);
-    }
-    else if (pl0.bm == 256 && pl0.bn == 128) launch_pair<4, 2>(pp, grid, st);
-    else if (pl0.bm == 128 && pl0.bn == 128) launch_pair<2, 2>(pp, grid, st);
-    else if (pl0.bm == 256 && pl0.bn == 64) launch_pair<4, 1>(pp, grid, st);
-    else if (pl0.bm == 128 && pl0.bn == 64) launch_pair<2, 1>(pp, grid, st);
-    else if (pl0.bm == 64 && pl0.bn == 128) launch_pair<1, 2>(pp, grid, st);
-    else launch_pair<1, 1>(pp, grid, st);
-    SG_CHECK_LAUNCH("sg_gemm_pair_f16");
-    if (int rc = launch_reduce(pp.p0, st)) return rc;
-    return launch_reduce(pp.p1, st);
-}
-
-extern "C" int sg_conv3x3_nhwc_f16(const sg_conv3x3_desc* d, sg_stream_t stream) {
-    SG_REQUIRE(d != nullptr, "sg_conv3x3: null descriptor");
-    SG_REQUIRE(d->x && d->w && d->y, "sg_conv3x3: null x/w/y");
-    SG_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "sg_conv3x3: bad shape");
-    SG_REQUIRE(d->Cin % 64 == 0, "sg_conv3x3: Cin (%d) must be a multiple of 64", d->Cin);
-    SG_REQUIRE(d->Cout % 8 == 0, "sg_conv3x3: Cout (%d) must be a multiple of 8", d->Cout);
-    SG_REQUIRE(d->stride == 1 || d->stride == 2, "sg_conv3x3: stride must be 1 or 2");
-    SG_REQUIRE(d->upsample2x == 0 || (d->upsample2x == 1 && d->stride == 1), "sg_conv3x3: upsample2x needs stride 1");
-    SG_REQUIRE(d->x_padded == 0 || d->x_padded == 1, "sg_conv3x3: x_padded must be 0 or 1");
-    SG_REQUIRE(d->ldx % 8 == 0 && d->ldx >= d->Cin, "sg_conv3x3: bad ldx");
-    SG_REQUIRE(sg_aligned16(d->x) && sg_aligned16(d->w), "sg_conv3x3: x/w must be 16-byte aligned");
-    if (int rc = check_out_res("sg_conv3x3", d->flags, d->y, d->ldy, nullptr, 0, d->res1, d->ldr1, nullptr, 0, d->Cout)) return rc;
-    SG_REQUIRE(!d->bias || sg_aligned16(d->bias), "sg_conv3x3: bias alignment");
-    SG_REQUIRE(!d->rowbias || (sg_aligned16(d->rowbias) && d->rowbias_ld % 4 == 0), "sg_conv3x3: rowbias alignment");
-    SG_REQUIRE(d->split_k >= 0 && d->split_k <= 64, "sg_conv3x3: split_k %d is outside the supported range [0, 64] (0 = auto, 1 = none)", d->split_k);
-    SG_REQUIRE(!d->workspace || sg_aligned16(d->workspace), "sg_conv3x3: workspace alignment");
-    SG_REQUIRE((int64_t)(d->W + 2) * d->ldx < (1 << 24), "sg_conv3x3: input row pitch must be below 2^24 elements");
+// Validates a convolution descriptor and translates it into kernel parameters (the twin of gemm_params).
+int conv_params(const sg_conv3x3_desc* d, MmaParams& p, const char* who) {
+    SG_REQUIRE(d != nullptr, "%s: null descriptor", who);
+    SG_REQUIRE(d->x && d->w && d->y, "%s: null x/w/y", who);
+    SG_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "%s: bad shape", who);
+    SG_REQUIRE(d->Cin % 64 == 0, "%s: Cin (%d) must be a multiple of 64", who, d->Cin);
+    SG_REQUIRE(d->Cout % 8 == 0, "%s: Cout (%d) must be a multiple of 8", who, d->Cout);
+    SG_REQUIRE(d->stride == 1 || d->stride == 2, "%s: stride must be 1 or 2", who);
+    SG_REQUIRE(d->upsample2x == 0 || (d->upsample2x == 1 && d->stride == 1), "%s: upsample2x needs stride 1", who);
+    SG_REQUIRE(d->x_padded == 0 || d->x_padded == 1, "%s: x_padded must be 0 or 1", who);
+    SG_REQUIRE(d->ldx % 8 == 0 && d->ldx >= d->Cin, "%s: bad ldx", who);
+    SG_REQUIRE(sg_aligned16(d->x) && sg_aligned16(d->w), "%s: x/w must be 16-byte aligned", who);
+    if (int rc = check_out_res(who, d->flags, d->y, d->ldy, nullptr, 0, d->res1, d->ldr1, nullptr, 0, d->Cout)) return rc;
+    SG_REQUIRE(!d->bias || sg_aligned16(d->bias), "%s: bias alignment", who);
+    SG_REQUIRE(!d->rowbias || (sg_aligned16(d->rowbias) && d->rowbias_ld % 4 == 0), "%s: rowbias alignment", who);
+    SG_REQUIRE(d->split_k >= 0 && d->split_k <= 64, "%s: split_k %d is outside the supported range [0, 64] (0 = auto, 1 = none)", who, d->split_k);
+    SG_REQUIRE(!d->workspace || sg_aligned16(d->workspace), "%s: workspace alignment", who);
+    SG_REQUIRE((int64_t)(d->W + 2) * d->ldx < (1 << 24), "%s: input row pitch must be below 2^24 elements", who);
     {
         // 32-bit LDS-DMA byte offsets (see gemm_params): the last byte of x — of the bordered [B, H+2, W+2] buffer with x_padded — and of
         // w lies below 4 GiB from its base pointer.  (pixels <= 2^31 is checked first: the products below then stay inside 64 bits.)
@@ -2031,15 +2004,15 @@ extern "C" int sg_conv3x3_nhwc_f16(const sg_conv3x3_desc* d, sg_stream_t stream)
         const long long x_span = pixels <= lim ? (pixels - 1) * (long long)d->ldx + d->Cin : lim + 1;
         const long long w_span = (long long)d->Cout * 9 * d->Cin;
         SG_REQUIRE(x_span <= lim,
-                   "sg_conv3x3: input x spans %s%lld elements ((pixels - 1) * ldx + Cin%s); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)",
-                   pixels <= lim ? "" : "more than ", x_span, d->x_padded ? ", zero border included" : "");
+                   "%s: input x spans %s%lld elements ((pixels - 1) * ldx + Cin%s); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)",
+                   who, pixels <= lim ? "" : "more than ", x_span, d->x_padded ? ", zero border included" : "");
         SG_REQUIRE(w_span <= lim,
-                   "sg_conv3x3: weights w span %lld elements (Cout * 9 * Cin); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)", w_span);
+                   "%s: weights w span %lld elements (Cout * 9 * Cin); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)", who, w_span);
     }
-    SG_REQUIRE(9 * (d->Cin / 64) < 3000, "sg_conv3x3: Cin (%d) too large for the slab decode (kt / 9 by multiply-shift, kt < 3000)", d->Cin);
+    SG_REQUIRE(9 * (d->Cin / 64) < 3000, "%s: Cin (%d) too large for the slab decode (kt / 9 by multiply-shift, kt < 3000)", who, d->Cin);
     const int hin = d->H << d->upsample2x, win = d->W << d->upsample2x;
     const int Ho = (hin + 2 - 3) / d->stride + 1, Wo = (win + 2 - 3) / d->stride + 1;
-    MmaParams p{};
+    p = MmaParams{};
     p.A = reinterpret_cast<const f16*>(d->x); p.lda = d->ldx;
     p.W = reinterpret_cast<const f16*>(d->w); p.ldw = 9L * d->Cin;
     p.C = d->y; p.ldc = d->ldy;
@@ -2050,12 +2023,122 @@ extern "C" int sg_conv3x3_nhwc_f16(const sg_conv3x3_desc* d, sg_stream_t stream)
     p.bias = reinterpret_cast<const f16*>(d->bias);
     p.rowbias = d->rowbias; p.rowbias_ld = d->rowbias_ld; p.rows_per_batch = Ho * Wo;
     p.res1 = d->res1; p.ldr1 = d->ldr1;
-    SG_REQUIRE(!d->stats || sg_aligned16(d->stats), "sg_conv3x3: stats alignment");
+    SG_REQUIRE(!d->stats || sg_aligned16(d->stats), "%s: stats alignment", who);
     p.stats = d->stats; p.stats_batch_rows = Ho * Wo;
-    SG_REQUIRE(d->defer_reduce == 0 || (d->defer_reduce == 1 && !d->stats), "sg_conv3x3: defer_reduce is 0 or 1 and excludes stats");
+    SG_REQUIRE(d->defer_reduce == 0 || (d->defer_reduce == 1 && !d->stats), "%s: defer_reduce is 0 or 1 and excludes stats", who);
     p.defer = d->defer_reduce;
-    if (int rc = check_tile_hint("sg_conv3x3", d->tile_m, d->tile_n, d->tile_waves)) return rc;
-    return launch_mma<true>(p, d->split_k, d->tile_m, d->tile_n, d->tile_waves, d->workspace, d->workspace_bytes, (hipStream_t)stream, "sg_conv3x3_nhwc_f16");
+    return check_tile_hint(who, d->tile_m, d->tile_n, d->tile_waves);
+}
+
+PlanRequest gemm_request(const sg_gemm_desc* d, const char* name) {
+    return PlanRequest{d->ln_mode ? 1 : d->split_k, TileHint{d->tile_m, d->tile_n, d->tile_waves}, d->workspace, d->workspace_bytes, name};
+}
+
+// validate -> plan, for the launching entry points and the queries alike (a query never launches)
+int plan_gemm(const sg_gemm_desc* d, MmaParams& p, Plan& pl, bool stats_optional = false, void* prof = nullptr) {
+    if (int rc = gemm_params(d, p, "sg_gemm_f16")) return rc;
+    PlanRequest rq = gemm_request(d, "sg_gemm_f16");
+    rq.stats_optional = stats_optional;
+    rq.prof = reinterpret_cast<unsigned long long*>(prof);
+    return plan_mma<false>(p, rq, pl);
+}
+
+int plan_conv(const sg_conv3x3_desc* d, MmaParams& p, Plan& pl, bool stats_optional = false, void* prof = nullptr) {
+    if (int rc = conv_params(d, p, "sg_conv3x3")) return rc;
+    PlanRequest rq{d->split_k, TileHint{d->tile_m, d->tile_n, d->tile_waves}, d->workspace, d->workspace_bytes, "sg_conv3x3_nhwc_f16"};
+    rq.stats_optional = stats_optional;
+    rq.prof = reinterpret_cast<unsigned long long*>(prof);
+    return plan_mma<true>(p, rq, pl);
+}
+
+// (the planner is asked about the launch, not about the deferral: a descriptor with defer_reduce plans like one without)
+int plan_conv_undeferred(const sg_conv3x3_desc* d, Plan& pl) {
+    sg_conv3x3_desc q = *d;
+    q.defer_reduce = 0;
+    MmaParams p;
+    return plan_conv(&q, p, pl);
+}
+
+// sg_gemm_pair_f16: one launch where one kernel instantiation serves both problems, else one launch each.
+struct PairPlan {
+    Plan pl0, pl1;
+    bool paired = false;
+    int grid = 0;           // of the paired launch (x extent times the two problems), 0 when not paired
+};
+
+int plan_pair(const sg_gemm_desc* d0, const sg_gemm_desc* d1, MmaPair& pp, PairPlan& out) {
+    if (int rc = gemm_params(d0, pp.p0, "sg_gemm_pair_f16[0]")) return rc;
+    if (int rc = gemm_params(d1, pp.p1, "sg_gemm_pair_f16[1]")) return rc;
+    SG_REQUIRE(!(d0->workspace && d1->workspace) ||
+               (reinterpret_cast<char*>(d0->workspace) + d0->workspace_bytes <= reinterpret_cast<char*>(d1->workspace) ||
+                reinterpret_cast<char*>(d1->workspace) + d1->workspace_bytes <= reinterpret_cast<char*>(d0->workspace)),
+               "sg_gemm_pair_f16: the two problems run concurrently and need disjoint workspaces");
+    PlanRequest rq0 = gemm_request(d0, "sg_gemm_pair_f16[0]"), rq1 = gemm_request(d1, "sg_gemm_pair_f16[1]");
+    rq0.in_pair = rq1.in_pair = true;
+    Plan &pl0 = out.pl0, &pl1 = out.pl1;
+    if (int rc = plan_mma<false>(pp.p0, rq0, pl0)) return rc;
+    // one kernel instantiation serves both problems: the second one is planned on the first one's tile shape (and kernel family)
+    PlanRequest on_tile0 = rq1;
+    on_tile0.hint = TileHint{pl0.bm, pl0.bn, pl0.lat() ? (pl0.bn == 128 ? 8 : 4) : -1};
+    if (int rc = plan_mma<false>(pp.p1, on_tile0, pl1)) return rc;
+    out.paired = pl0.family != FAM_GENERIC && pl1.family != FAM_GENERIC && pl1.bm == pl0.bm && pl1.bn == pl0.bn && pl0.lat() == pl1.lat() &&
+                 !(pl0.lat() && pl0.bn == 128);
+    if (!out.paired) {      // not pairable (K % 64, forced tile): two launches, the second problem on its own hints
+        out.grid = 0;
+        return plan_mma<false>(pp.p1, rq1, pl1);
+    }
+    // grid.x is a multiple of 8 so that block (x, 1) sits on XCD x % 8 like block (x, 0): xcd_remap keeps its meaning
+    out.grid = (((pl0.grid > pl1.grid ? pl0.grid : pl1.grid) + 7) & ~7) * 2;
+    return SG_OK;
+}
+
+template <int WGM, int WGN>
+void launch_pair(const MmaPair& pp, dim3 grid, dim3 block, hipStream_t st) {
+    hipLaunchKernelGGL((mma_pipe_pair_kernel<WGM, WGN>), grid, block, 0, st, pp);
+}
+
+// Launches a paired plan (both problems on pl0's tile and family): the one place that maps it to a kernel instantiation.
+int launch_pair_plan(const MmaPair& pp, const PairPlan& pr, hipStream_t st) {
+    const Plan& pl0 = pr.pl0;
+    const dim3 grid(pr.grid / 2, 2), block(pl0.threads);
+    if (pl0.lat()) {
+        if (pl0.ring() == 8) hipLaunchKernelGGL(mma_lat_pair_kernel<8>, grid, block, 0, st, pp);
+        else hipLaunchKernelGGL(mma_lat_pair_kernel<4>, grid, block, 0, st, pp);
+    }
+    else if (pl0.bm == 256 && pl0.bn == 128) launch_pair<4, 2>(pp, grid, block, st);
+    else if (pl0.bm == 128 && pl0.bn == 128) launch_pair<2, 2>(pp, grid, block, st);
+    else if (pl0.bm == 256 && pl0.bn == 64) launch_pair<4, 1>(pp, grid, block, st);
+    else if (pl0.bm == 128 && pl0.bn == 64) launch_pair<2, 1>(pp, grid, block, st);
+    else if (pl0.bm == 64 && pl0.bn == 128) launch_pair<1, 2>(pp, grid, block, st);
+    else launch_pair<1, 1>(pp, grid, block, st);
+    SG_CHECK_LAUNCH("sg_gemm_pair_f16");
+    if (int rc = launch_reduce(pp.p0, st)) return rc;
+    return launch_reduce(pp.p1, st);
+}
+}  // namespace
+
+extern "C" int sg_gemm_f16(const sg_gemm_desc* d, sg_stream_t stream) {
+    MmaParams p;
+    Plan pl;
+    if (int rc = plan_gemm(d, p, pl)) return rc;
+    return launch_plan<false>(p, pl, (hipStream_t)stream, "sg_gemm_f16");
+}
+
+extern "C" int sg_gemm_pair_f16(const sg_gemm_desc* d0, const sg_gemm_desc* d1, sg_stream_t stream) {
+    MmaPair pp;
+    PairPlan pr;
+    if (int rc = plan_pair(d0, d1, pp, pr)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (pr.paired) return launch_pair_plan(pp, pr, st);
+    if (int rc = launch_plan<false>(pp.p0, pr.pl0, st, "sg_gemm_pair_f16[0]")) return rc;
+    return launch_plan<false>(pp.p1, pr.pl1, st, "sg_gemm_pair_f16[1]");
+}
+
+extern "C" int sg_conv3x3_nhwc_f16(const sg_conv3x3_desc* d, sg_stream_t stream) {
+    MmaParams p;
+    Plan pl;
+    if (int rc = plan_conv(d, p, pl)) return rc;
+    return launch_plan<true>(p, pl, (hipStream_t)stream, "sg_conv3x3_nhwc_f16");
 }
 
 // Would a launch with this descriptor emit epilogue statistics, and with which tile height?  (Plans the launch exactly as
@@ -2063,49 +2146,59 @@ extern "C" int sg_conv3x3_nhwc_f16(const sg_conv3x3_desc* d, sg_stream_t stream)
 // launching.)  Returns the rows per partial (> 0), 0 when the launch cannot emit them, < 0 on an invalid descriptor.
 extern "C" int sg_gemm_stats_tile_rows(const sg_gemm_desc* d) {
     SG_REQUIRE(d && d->stats, "sg_gemm_stats_tile_rows: descriptor with a stats buffer required");
-    g_stats_query = true; g_query_rows = 0;
-    const int rc = sg_gemm_f16(d, nullptr);
-    g_stats_query = false;
-    return rc ? rc : g_query_rows;
-}
-
-extern "C" int sg_conv3x3_planned_splits(const sg_conv3x3_desc* d) {
-    SG_REQUIRE(d != nullptr, "sg_conv3x3_planned_splits: null descriptor");
-    sg_conv3x3_desc q = *d;
-    q.defer_reduce = 0;
-    g_plan_query = true; g_query_rows = 0;
-    const int rc = sg_conv3x3_nhwc_f16(&q, nullptr);
-    g_plan_query = false;
-    return rc ? rc : g_query_rows;
-}
-
-// The decomposition a launch with this descriptor will use (host-only, no launch): out[6] = {tile rows, tile columns, K slices,
-// workgroups, threads per workgroup, 1 if the LDS-DMA kernel applies}.  Measurement tooling joins it with a profiler's (kernel,
-// grid) classes (tools/traffic_from_pmc.py: algorithmic bytes per class).
-extern "C" int sg_gemm_launch_plan(const sg_gemm_desc* d, int32_t* out) {
-    SG_REQUIRE(d && out, "sg_gemm_launch_plan: null argument");
-    g_plan_query = true; g_query_rows = 0; g_plan_out = out;
-    const int rc = sg_gemm_f16(d, nullptr);
-    g_plan_query = false; g_plan_out = nullptr;
-    return rc;
-}
-
-extern "C" int sg_conv3x3_launch_plan(const sg_conv3x3_desc* d, int32_t* out) {
-    SG_REQUIRE(d && out, "sg_conv3x3_launch_plan: null argument");
-    sg_conv3x3_desc q = *d;
-    q.defer_reduce = 0;
-    g_plan_query = true; g_query_rows = 0; g_plan_out = out;
-    const int rc = sg_conv3x3_nhwc_f16(&q, nullptr);
-    g_plan_query = false; g_plan_out = nullptr;
-    return rc;
+    MmaParams p;
+    Plan pl;
+    const int rc = plan_gemm(d, p, pl, true);
+    return rc ? rc : pl.stats_rows;
 }
 
 extern "C" int sg_conv3x3_stats_tile_rows(const sg_conv3x3_desc* d) {
     SG_REQUIRE(d && d->stats, "sg_conv3x3_stats_tile_rows: descriptor with a stats buffer required");
-    g_stats_query = true; g_query_rows = 0;
-    const int rc = sg_conv3x3_nhwc_f16(d, nullptr);
-    g_stats_query = false;
-    return rc ? rc : g_query_rows;
+    MmaParams p;
+    Plan pl;
+    const int rc = plan_conv(d, p, pl, true);
+    return rc ? rc : pl.stats_rows;
+}
+
+extern "C" int sg_conv3x3_planned_splits(const sg_conv3x3_desc* d) {
+    SG_REQUIRE(d != nullptr, "sg_conv3x3_planned_splits: null descriptor");
+    Plan pl;
+    const int rc = plan_conv_undeferred(d, pl);
+    return rc ? rc : pl.splits;
+}
+
+// The decomposition a launch with this descriptor will use (host-only, no launch): out[6] = {tile rows, tile columns, K slices,
+// workgroups, threads per workgroup, kernel family (FAM_*)}.  Measurement tooling joins it with a profiler's (kernel, grid) classes
+// (tools/traffic_from_pmc.py: algorithmic bytes per class).
+extern "C" int sg_gemm_launch_plan(const sg_gemm_desc* d, int32_t* out) {
+    SG_REQUIRE(d && out, "sg_gemm_launch_plan: null argument");
+    MmaParams p;
+    Plan pl;
+    if (int rc = plan_gemm(d, p, pl)) return rc;
+    report_plan(pl, out);
+    return SG_OK;
+}
+
+extern "C" int sg_conv3x3_launch_plan(const sg_conv3x3_desc* d, int32_t* out) {
+    SG_REQUIRE(d && out, "sg_conv3x3_launch_plan: null argument");
+    Plan pl;
+    if (int rc = plan_conv_undeferred(d, pl)) return rc;
+    report_plan(pl, out);
+    return SG_OK;
+}
+
+// The same for sg_gemm_pair_f16: out[14] = {1 if one launch serves both problems, the six integers of problem 0, of problem 1 (each
+// as launched: on problem 0's tile when paired, on its own plan otherwise), workgroups of the paired launch or 0}.
+extern "C" int sg_gemm_pair_launch_plan(const sg_gemm_desc* d0, const sg_gemm_desc* d1, int32_t* out) {
+    SG_REQUIRE(out, "sg_gemm_pair_launch_plan: null argument");
+    MmaPair pp;
+    PairPlan pr;
+    if (int rc = plan_pair(d0, d1, pp, pr)) return rc;
+    out[0] = pr.paired;
+    report_plan(pr.pl0, out + 1);
+    report_plan(pr.pl1, out + 7);
+    out[13] = pr.grid;
+    return SG_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ diagnostics
@@ -2115,10 +2208,10 @@ extern "C" int sg_conv3x3_stats_tile_rows(const sg_conv3x3_desc* d) {
 extern "C" int sg_debug_gemm_anatomy(const sg_gemm_desc* d, void* prof, size_t prof_bytes, sg_stream_t stream) {
 #ifdef SG_BUILD_EXPERIMENTS
     SG_REQUIRE(d && prof && prof_bytes >= (size_t)8 * 10 * 8 * 65536 / 64, "sg_debug_gemm_anatomy: need a profile buffer (>= 80 B per wave)");
-    g_prof = reinterpret_cast<unsigned long long*>(prof);
-    const int rc = sg_gemm_f16(d, stream);
-    g_prof = nullptr;
-    return rc;
+    MmaParams p;
+    Plan pl;
+    if (int rc = plan_gemm(d, p, pl, false, prof)) return rc;
+    return launch_plan<false>(p, pl, (hipStream_t)stream, "sg_gemm_f16");
 #else
     (void)d; (void)prof; (void)prof_bytes; (void)stream;
     return sg_set_error(SG_EINVAL, "sg_debug_gemm_anatomy: this library was built without SG_BUILD_EXPERIMENTS");
@@ -2128,10 +2221,10 @@ extern "C" int sg_debug_gemm_anatomy(const sg_gemm_desc* d, void* prof, size_t p
 extern "C" int sg_debug_conv_anatomy(const sg_conv3x3_desc* d, void* prof, size_t prof_bytes, sg_stream_t stream) {
 #ifdef SG_BUILD_EXPERIMENTS
     SG_REQUIRE(d && prof && prof_bytes >= (size_t)8 * 10 * 8 * 65536 / 64, "sg_debug_conv_anatomy: need a profile buffer (>= 80 B per wave)");
-    g_prof = reinterpret_cast<unsigned long long*>(prof);
-    const int rc = sg_conv3x3_nhwc_f16(d, stream);
-    g_prof = nullptr;
-    return rc;
+    MmaParams p;
+    Plan pl;
+    if (int rc = plan_conv(d, p, pl, false, prof)) return rc;
+    return launch_plan<true>(p, pl, (hipStream_t)stream, "sg_conv3x3_nhwc_f16");
 #else
     (void)d; (void)prof; (void)prof_bytes; (void)stream;
     return sg_set_error(SG_EINVAL, "sg_debug_conv_anatomy: this library was built without SG_BUILD_EXPERIMENTS");
@@ -2139,7 +2232,8 @@ extern "C" int sg_debug_conv_anatomy(const sg_conv3x3_desc* d, void* prof, size_
 }
 
 extern "C" int sg_debug_set_tile(int32_t bm, int32_t bn, int32_t no_pipe) {
-    g_tune.bm = bm; g_tune.bn = bn; g_tune.no_pipe = no_pipe;
+    SgOptions& o = sg_options();
+    o.tile_m = bm; o.tile_n = bn; o.no_pipe = no_pipe;
     return SG_OK;
 }
 

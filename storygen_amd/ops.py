@@ -284,29 +284,23 @@ def _kernel_name(bm: int, bn: int, pipe: int, conv: bool) -> str:
 
 
 def _report_plan(kind: str, d, nbytes: float, family: str, shape: str, second=None):
-    """PLAN_SINK record of one launch (see PLAN_SINK).  second = (desc, bytes) of the other problem of a paired launch.  Plans are
-    queried on COPIES of the descriptors: the instrumented step must launch exactly what the uninstrumented one does."""
-    if kind == "conv":
-        bm, bn, splits, wgs, threads, pipe = _plan_of(lib.sg_conv3x3_launch_plan, d)
-        name = _kernel_name(bm, bn, pipe, True)
+    """PLAN_SINK record of one launch (see PLAN_SINK).  second = (desc, bytes) of the other problem of a paired launch
+    (sg_gemm_pair_launch_plan says whether the two share a launch).  The queries launch nothing and leave the descriptors as they are:
+    the instrumented step launches exactly what the uninstrumented one does."""
+    if second is not None:
+        d1, b1 = second
+        out = (C.c_int32 * 14)()
+        check(lib.sg_gemm_pair_launch_plan(C.byref(d), C.byref(d1), out), "launch plan")
+        (bm, bn, _, wgs, threads, pipe), (bm1, bn1, _, wgs1, threads1, pipe1) = out[1:7], out[7:13]
+        if out[0]:
+            name = f"mma_lat_pair_kernel<{pipe - 16}>" if pipe >= 16 else f"mma_pipe_pair_kernel<{bm // 64}, {bn // 64}>"
+            PLAN_SINK.append((name, out[13] * threads, nbytes + b1, family, shape))
+            return
+        # not pairable: two plain launches, each on its own plan
+        PLAN_SINK.append((_kernel_name(bm1, bn1, pipe1, False), wgs1 * threads1, b1, family, shape + " [2nd]"))
     else:
-        bm, bn, splits, wgs, threads, pipe = _plan_of(lib.sg_gemm_launch_plan, d)
-        name = _kernel_name(bm, bn, pipe, False)
-        if second is not None:
-            d1, b1 = second
-            q = type(d1).from_buffer_copy(d1)
-            q.tile_m, q.tile_n, q.tile_waves = bm, bn, ((8 if bn == 128 else 4) if pipe >= 16 else 0)
-            bm1, bn1, _, wgs1, threads1, pipe1 = _plan_of(lib.sg_gemm_launch_plan, q)
-            if pipe and pipe1 and (bm1, bn1) == (bm, bn) and (pipe >= 16) == (pipe1 >= 16):
-                if pipe >= 16:
-                    name = f"mma_lat_pair_kernel<{pipe - 16}>"
-                else:
-                    name = f"mma_pipe_pair_kernel<{bm // 64}, {bn // 64}>"
-                wgs, nbytes = ((max(wgs, wgs1) + 7) & ~7) * 2, nbytes + b1
-            else:           # not pairable: two plain launches, each on its own plan
-                bm1, bn1, _, wgs1, threads1, pipe1 = _plan_of(lib.sg_gemm_launch_plan, d1)
-                PLAN_SINK.append((_kernel_name(bm1, bn1, pipe1, False), wgs1 * threads1, b1, family, shape + " [2nd]"))
-    PLAN_SINK.append((name, wgs * threads, nbytes, family, shape))
+        bm, bn, _, wgs, threads, pipe = _plan_of(lib.sg_conv3x3_launch_plan if kind == "conv" else lib.sg_gemm_launch_plan, d)
+    PLAN_SINK.append((_kernel_name(bm, bn, pipe, kind == "conv"), wgs * threads, nbytes, family, shape))
 
 
 def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, **kw) -> torch.Tensor:

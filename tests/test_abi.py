@@ -175,6 +175,27 @@ def test_forced_split_plans_and_operand_bound_on_the_host(lib):
         assert conv(h_out, 2 ** 22 - 8, padded, 1)[0] == -1 and b"input x" in lib.sg_last_error() and b"2^31" in lib.sg_last_error()
 
 
+def test_launch_plans_match_the_recording(lib):
+    """The planner is a pure function of descriptor and development options: tools/dump_launch_plans.py asks it (plan, statistics rows,
+    K slices, pair decision, error texts — host-only queries) over a sweep that reaches every branch of the tile / family / split
+    choice; tests/golden/launch_plans.json is that sweep's answer from the library before the planner became plain values (pairs:
+    sg_gemm_pair_f16's rule restated on single-problem queries).  Row by row the same."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("dump_launch_plans", os.path.join(ROOT, "tools", "dump_launch_plans.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    with open(os.path.join(ROOT, "tests", "golden", "launch_plans.json")) as f:
+        want = json.load(f)
+    got = json.loads(json.dumps(mod.sweep(lib)))
+    assert [s["options"] for s in got] == [s["options"] for s in want]
+    for g, w in zip(got, want):
+        assert [r["id"] for r in g["rows"]] == [r["id"] for r in w["rows"]], g["options"]
+        for rg, rw in zip(g["rows"], w["rows"]):
+            assert rg == rw, (g["options"], rw, rg)
+    assert sum(len(s["rows"]) for s in want) == 1436
+
+
 def test_backward_entry_points_validate_on_the_host(lib):
     """Same for the backward-pass entry points (BASELINE config 4): bad descriptors are refused before any launch."""
     from storygen_amd._lib import AttnBwdDesc, AttnDesc, GroupNormBwdDesc
