@@ -454,6 +454,24 @@ int sg_copy_rows(void* dst, int64_t ldd, int64_t bsd, const void* src, int64_t l
 int sg_pad_cast_f16(const void* x, int64_t ldx, int32_t x_f32, sg_half* y, int64_t ldy, int32_t B, int32_t H, int32_t W,
                     int32_t C, sg_stream_t stream);
 
+/* Story generation: the frame hand-off.  One launch turns the VAE decoder's output x — fp16 NCHW [N, 3, H, W], roughly in [-1, 1];
+ * batch / channel / row strides bsx / csx / ldx in elements, unit pixel stride, so a window of a larger buffer works — into
+ *   u8: the frame as saved, uint8 NHWC [N, H, W, 3] (batch / row strides bsu / ldu in bytes, pixel stride 3): bit for bit what
+ *       numpy_to_pil(decode_latents(.)) of the pipeline stores — x / 2 and + 0.5 each rounded to fp16, clamp(0, 1), widened to fp32,
+ *       * 255 in fp32, rounded half to even, narrowed;
+ *   y:  the next call's image_prompt entry, fp16 NCHW [N, 3, H, W] (strides bsy / csy / ldy), y = fp16(fp32(u8) / 255) in [0, 1]:
+ *       what ToTensor of the saved image followed by the pipeline's cast gives.
+ * +-inf clamp like any large value; a NaN input gives 0 in both outputs.  Rows of 8 pixels move as 16-byte loads / stores where x and
+ * y are 16-byte aligned with strides that are multiples of 8 (u8 as 8-byte stores where its rows are 8-byte aligned), anything else
+ * element by element: no alignment is required.  Nothing outside the [N, 3, H, W] / [N, H, W, 3] windows is touched.
+ * SG_EINVAL before any launch: a null pointer, N <= 0, H * W == 0, strides that make a tensor overlap itself (row < W, channel <
+ * (H - 1) * row + W, ...), outputs that overlap each other or the input.
+ * Grid-stride over N * H * (W / 8 + W % 8) work items (N * H * W without the vector path): at most SG_FRAME_HANDOFF_MAX_BLOCKS
+ * workgroups of 256. */
+#define SG_FRAME_HANDOFF_MAX_BLOCKS 1024
+int sg_frame_handoff_f16(const sg_half* x, int64_t bsx, int64_t csx, int64_t ldx, uint8_t* u8, int64_t bsu, int64_t ldu,
+                         sg_half* y, int64_t bsy, int64_t csy, int64_t ldy, int32_t N, int32_t H, int32_t W, sg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * The networks either side of the loop: CLIP text encoder and AutoencoderKL.  Their GEMMs, convolutions,
  * GroupNorms and LayerNorms are the entry points above; these are the remaining pieces.

@@ -21,16 +21,22 @@ Deliberate differences from the reference, none of which changes latents:
 """
 from __future__ import annotations
 
-from collections import namedtuple
+from collections import OrderedDict, namedtuple
 from typing import Callable, List, Optional, Union
 
 import torch
 
+from .. import ops
 from ..sampler import STAGES, StoryGenSampler
 from ..scheduler import DDIMSchedule, schedule_from_config
 from .encoders import _HipModule
 
 StableDiffusionPipelineOutput = namedtuple("StableDiffusionPipelineOutput", ["images", "nsfw_content_detected"])
+# Samplers kept per pipeline, by key (the number of prior frames R is part of it).  A story alternates R = 0 (stage "no"), 1, 2, 3, 3, ...
+# (storygen_amd/story.py): with one entry every frame of its head would rebuild a sampler and recapture its hipGraphs.  Four entries,
+# the oldest evicted; a caller that repeats one call sees what it saw with one entry (same key, same sampler object).  DESIGN §9 x6 has
+# the memory this holds at 512 x 512.
+SAMPLER_CACHE_ENTRIES = 4
 
 
 def _as_schedule(scheduler) -> DDIMSchedule:
@@ -51,8 +57,8 @@ class StableDiffusionPipeline:
         self.vae, self.text_encoder, self.tokenizer, self.unet, self.scheduler = vae, text_encoder, tokenizer, unet, scheduler
         boc = getattr(getattr(vae, "config", None), "block_out_channels", (128, 256, 512, 512))
         self.vae_scale_factor = 2 ** (len(boc) - 1)                                       # :76
-        self._sampler: Optional[StoryGenSampler] = None
-        self._sampler_key = None
+        self._samplers: "OrderedDict[tuple, StoryGenSampler]" = OrderedDict()      # in construction order
+        self._sampler_key = None                                                  # the last call's
         self._progress_bar_config = {}
 
     def hip_encoders(self):
@@ -63,6 +69,23 @@ class StableDiffusionPipeline:
         if isinstance(self.text_encoder, torch.nn.Module):
             self.text_encoder = CLIPTextModel.from_torch(self.text_encoder).to(self._execution_device)
         return self
+
+    # --------------------------------------------------------------------------------------------- sampler cache
+    @property
+    def _sampler(self) -> Optional[StoryGenSampler]:
+        """The sampler of the last call (None before the first)."""
+        return self._samplers.get(self._sampler_key)
+
+    def _sampler_for(self, key, make) -> StoryGenSampler:
+        """The cached sampler of `key`, or make() kept under it; beyond SAMPLER_CACHE_ENTRIES the oldest (first built) entry goes."""
+        smp = self._samplers.get(key)
+        if smp is None:
+            smp = make()
+            while len(self._samplers) >= SAMPLER_CACHE_ENTRIES:
+                self._samplers.popitem(last=False)
+            self._samplers[key] = smp
+        self._sampler_key = key
+        return smp
 
     # --------------------------------------------------------------------------------------------- plumbing
     @property
@@ -210,6 +233,17 @@ class StableDiffusionPipeline:
         image = (image / 2 + 0.5).clamp(0, 1)
         return image.cpu().permute(0, 2, 3, 1).float().numpy()
 
+    def _decode_device(self, latents):
+        """decode_latents + numpy_to_pil + the reload of the saved image (inference.py:86-92), without leaving the device: latents ->
+        (uint8 [N,H,W,3] frames, equal to numpy_to_pil(decode_latents(latents)) bit for bit; fp16 [N,3,H,W] frames in [0, 1], the
+        next call's `image_prompt` entries) — ops.frame_handoff on the decoder's output.  The decoder must run in fp16, the reference's
+        mixed_precision (inference.py:35,73): the hand-off reproduces decode_latents' fp16 roundings and has no other form."""
+        image = self.vae.decode(latents / 0.18215).sample
+        if image.dtype != torch.float16:
+            raise TypeError(f"_decode_device: the VAE decoder returned {image.dtype}; the frame hand-off kernel takes fp16 (run the "
+                            f"pipeline in fp16, as the reference's inference.py does)")
+        return ops.frame_handoff(image)
+
     @staticmethod
     def numpy_to_pil(images):
         from PIL import Image
@@ -268,12 +302,11 @@ class StableDiffusionPipeline:
         rule = schedule.update_rule(float(eta))
         eta = rule.eta
         variance_noise = self._variance_noise(latents, evals, generator) if rule.needs_noise and eta > 0 else None
-        key = (n, h, w, R, text.shape[1], id(wts), schedule.key(), G, eta, rule.key)
-        if self._sampler is None or self._sampler_key != key:
-            self._sampler = StoryGenSampler(self.unet._arch, None, device, n, h, w, R, text.shape[1], schedule=schedule, weights=wts,
-                                            ref_ahead=G)
-            self._sampler_key = key
-        smp = self._sampler
+        # (stage "no" has its own entry: one sampler asked for another layout rebuilds its engines and recaptures its graphs, and a
+        # story's text-only first frame and its one-prior-frame second frame otherwise share every other field when G = 1)
+        key = (n, h, w, R, text.shape[1], id(wts), schedule.key(), G, eta, rule.key, stage == "no")
+        smp = self._sampler_for(key, lambda: StoryGenSampler(self.unet._arch, None, device, n, h, w, R, text.shape[1], schedule=schedule,
+                                                             weights=wts, ref_ahead=G))
         smp.prepare(inputs, num_inference_steps, stage, guidance_scale, image_guidance_scale, eta=eta, variance_noise=variance_noise)
         with self.progress_bar(total=len(smp.timesteps)) as bar:
             for i, t in enumerate(smp.timesteps):                                         # :411-469

@@ -952,6 +952,39 @@ def pad_cast(x: torch.Tensor, out_padded: torch.Tensor) -> torch.Tensor:
     return out_padded
 
 
+FRAME_HANDOFF_MAX_BLOCKS = 1024          # SG_FRAME_HANDOFF_MAX_BLOCKS: the grid-stride loop wraps above this many workgroups of 256
+
+
+def frame_handoff(x: torch.Tensor, out_u8: Optional[torch.Tensor] = None, out_f16: Optional[torch.Tensor] = None):
+    """The VAE decoder's output x, fp16 [N,3,H,W] roughly in [-1,1] (any batch / channel / row stride, unit pixel stride) ->
+    (the frames as saved, uint8 [N,H,W,3]; the same frames as the next call's `image_prompt` entries, fp16 [N,3,H,W] in [0,1]),
+    sg_frame_handoff_f16.  The uint8 frame equals numpy_to_pil(decode_latents(.)) of model/pipeline.py bit for bit; the fp16 frame is
+    fp16(fp32(uint8) / 255), what the reference's inference.py:86-92 feeds back from the saved image — in [0, 1]: the `* 2 - 1` of
+    inference.py:90-91 rebinds its loop variable and is never applied to the tensor, and that convention is kept.  NaN -> 0 in both.
+    Outputs are allocated when not given; given ones may be windows of larger buffers ([N,H,W,3] with pixel stride 3, [N,3,H,W] with
+    unit pixel stride)."""
+    _f16(x, "x")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"frame_handoff: x must be [N,3,H,W], got {tuple(x.shape)}")
+    N, _, H, W = x.shape
+    if out_u8 is None:
+        out_u8 = torch.empty(N, H, W, 3, dtype=torch.uint8, device=x.device)
+    if out_f16 is None:
+        out_f16 = torch.empty(N, 3, H, W, dtype=torch.float16, device=x.device)
+    _f16(out_f16, "out_f16")
+    if out_u8.dtype != torch.uint8 or not out_u8.is_cuda:
+        raise TypeError(f"out_u8: expected a CUDA/HIP uint8 tensor, got {out_u8.dtype} on {out_u8.device}")
+    if tuple(out_u8.shape) != (N, H, W, 3) or tuple(out_f16.shape) != (N, 3, H, W):
+        raise ValueError(f"frame_handoff: outputs must be [N,H,W,3] and [N,3,H,W] for x {tuple(x.shape)}")
+    if N * H * W:      # (strides of an empty tensor say nothing; the library refuses the empty shape itself)
+        if x.stride(3) != 1 or out_f16.stride(3) != 1 or out_u8.stride(3) != 1 or out_u8.stride(2) != 3:
+            raise ValueError("frame_handoff: unit pixel stride on x and out_f16, [.., W, 3] contiguous pixels on out_u8")
+    check(lib.sg_frame_handoff_f16(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), out_u8.data_ptr(), out_u8.stride(0), out_u8.stride(1),
+                                   out_f16.data_ptr(), out_f16.stride(0), out_f16.stride(1), out_f16.stride(2), N, H, W, _stream()),
+          "sg_frame_handoff_f16")
+    return out_u8, out_f16
+
+
 # ------------------------------------------------------------------------------------------------ backward pass (config 4)
 # Validated on MI355X in round 2 (tests/test_backward_gpu.py).  Kernels: csrc/backward.hip, attention_bwd.hip; formulas: oracle/storygen_backward.py.
 def layernorm_bwd(x: torch.Tensor, dy1: torch.Tensor, g1: torch.Tensor, out: torch.Tensor, eps: float = 1e-5,

@@ -8,6 +8,11 @@ a stand-in tokenizer (token ids are irrelevant for timing).  Prints one JSON lin
     python tools/bench_pipeline.py --compare ddim:40,ddim:50,dpm:20,dpm:25,ddim:40:0.5 [--rounds 5]      (a third field = eta)
         several configurations in one process (one pipeline each, sharing the networks), timed in alternation round by round so that
         drift of the machine spreads over all of them; one JSON line per configuration with every sample.
+    python tools/bench_pipeline.py --story K [STEPS] [--rounds 3]
+        a K-frame story (storygen_amd.story.StoryGenerator, context_frames 3, one sample per frame, no scorer) against the same K frames
+        as chained pipeline calls with the host round trip of inference.py (PIL image, PNG in memory, reload, ToTensor, upload), timed in
+        alternation; one JSON line with both totals, the per-frame times, and the story's split into encode (text encoder + VAE
+        encoder), loop, decode, hand-off and scoring from one extra run with a device synchronisation around each part.
 dpm = DPM-Solver++(2M), diffusers' DPMSolverMultistepScheduler defaults (storygen_amd.scheduler.DPMSolverMultistepSchedule)."""
 import argparse
 import json
@@ -44,6 +49,7 @@ def main():
                                                            "generator inside the timed call, as a user's call draws it)")
     ap.add_argument("--compare", default="", help="comma-separated scheduler:steps[:eta] list, timed in alternation")
     ap.add_argument("--rounds", type=int, default=3, help="timed calls per configuration")
+    ap.add_argument("--story", type=int, default=0, metavar="K", help="time a K-frame story against K chained calls with the host round trip")
     args = ap.parse_args()
     def parse(c):
         f = c.split(":")
@@ -57,6 +63,8 @@ def main():
     vae = AutoencoderKL(block_out_channels=(128, 256, 512, 512), down_block_types=("DownEncoderBlock2D",) * 4,
                         up_block_types=("UpDecoderBlock2D",) * 4, layers_per_block=2).to(dev, f16)
     clip = CLIPTextModel(dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12)).to(dev, f16)
+    if args.story:
+        return story(args, unet, vae, clip, dev)
     frames = torch.rand(1, 3, 3, 512, 512)
     pipes = []
     for name, steps, _ in configs:          # one pipeline (hence one cached sampler and its graphs) per configuration
@@ -90,6 +98,111 @@ def main():
                           "seconds_max": round(srt[-1], 4), "seconds_all": [round(v, 4) for v in samples],
                           "ms_per_step_incl_everything": round(med / steps * 1e3, 2), "image_shape": list(img.shape),
                           "finite": bool(torch.isfinite(torch.as_tensor(img)).all())}))
+
+
+def story(args, unet, vae, clip, dev):
+    import io
+
+    import numpy as np
+    from PIL import Image
+
+    from storygen_amd import ops
+    from storygen_amd.story import StoryGenerator
+    K, steps, cf = args.story, args.steps, 3
+    prompts = [f"frame {j}" for j in range(K)]
+    pipe = StableDiffusionPipeline(vae=vae, text_encoder=clip, tokenizer=Tok(), unet=unet, scheduler=SCHEDULERS[args.scheduler][1]())
+    pipe.set_progress_bar_config(disable=True)
+    gen = StoryGenerator(pipe)
+    kw = dict(num_inference_steps=steps, guidance_scale=7.0, image_guidance_scale=3.5, height=512, width=512)
+    marks, mem = [], []
+
+    def run_story():
+        torch.manual_seed(0)
+        marks.clear()
+        real = pipe._decode_device
+
+        def decode(lat):                       # per-frame times: the host reaches this point once per frame
+            out = real(lat)
+            torch.cuda.synchronize()
+            marks.append(time.perf_counter())
+            mem.append(torch.cuda.memory_allocated())
+            return out
+        pipe._decode_device = decode
+        try:
+            return gen.generate(prompts, context_frames=cf, generator=torch.Generator(device=dev).manual_seed(1), output_type="uint8", **kw).frames
+        finally:
+            del pipe._decode_device
+
+    def run_chained():
+        torch.manual_seed(0)
+        marks.clear()
+        g, pil = torch.Generator(device=dev).manual_seed(1), []
+        for j, p in enumerate(prompts):
+            prior = list(range(max(0, j - cf), j))
+            if prior:
+                reloaded = []
+                for i in prior:                # inference.py:86-92 on the saved file (here a PNG in memory)
+                    buf = io.BytesIO()
+                    pil[i].save(buf, format="PNG")
+                    buf.seek(0)
+                    reloaded.append(torch.from_numpy(np.asarray(Image.open(buf).convert("RGB")).copy()).permute(2, 0, 1).float() / 255)
+                stage, ip, prev = "auto-regressive", torch.stack(reloaded).unsqueeze(0), [prompts[i] for i in prior]
+            else:
+                stage, ip, prev = "no", torch.zeros(1, 1, 3, 512, 512), [p]
+            pil.append(pipe(stage=stage, prompt=p, image_prompt=ip, prev_prompt=prev, generator=g, output_type="pil", **kw).images[0])
+            marks.append(time.perf_counter())
+        return np.stack([np.asarray(im) for im in pil])
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, time.perf_counter() - t0, [round(b - a, 4) for a, b in zip([t0] + marks[:-1], marks)]
+
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    a, first_story_s, _ = timed(run_story)               # builds the samplers, captures the graphs
+    held = torch.cuda.memory_allocated() - base
+    grown = [m - n for m, n in zip(mem, [base] + mem[:-1])]      # frame 0: repacked UNet weights + the stage-"no" sampler; then one new sampler per frame
+    b, _, _ = timed(run_chained)
+    res = {"story": [], "chained": []}
+    for _ in range(args.rounds):
+        for name, fn in (("story", run_story), ("chained", run_chained)):
+            _, t, per = timed(fn)
+            res[name].append((t, per))
+    # the split: one more story with a synchronisation around each part (not one of the timed runs)
+    split = {"encode": 0.0, "decode": 0.0, "handoff": 0.0, "scoring": 0.0}
+
+    def part(name, fn):
+        def wrapped(*a_, **k_):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(*a_, **k_)
+            torch.cuda.synchronize()
+            split[name] += time.perf_counter() - t0
+            return out
+        return wrapped
+    real_handoff = ops.frame_handoff
+    pipe._encode_prompt, vae.encode, vae.decode = part("encode", pipe._encode_prompt), part("encode", vae.encode), part("decode", vae.decode)
+    ops.frame_handoff = part("handoff", real_handoff)
+    try:
+        _, total, _ = timed(run_story)
+    finally:
+        ops.frame_handoff = real_handoff
+        del pipe._encode_prompt, vae.encode, vae.decode
+    split["loop"] = total - sum(split.values())
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    out = {"workload": f"{K}-frame story, {steps} {SCHEDULERS[args.scheduler][0]} steps per frame, 512x512, context_frames {cf}, one sample per "
+                       "frame, no scorer, HIP CLIP + VAE + UNet, fp16; chained = the same frames as pipeline calls with the host round trip "
+                       "(PIL, PNG in memory, reload, ToTensor, upload)",
+           "frames": K, "steps": steps, "frames_identical": bool(np.array_equal(a, b)),
+           "story_seconds_median": round(med([t for t, _ in res["story"]]), 4), "chained_seconds_median": round(med([t for t, _ in res["chained"]]), 4),
+           "story_seconds_all": [round(t, 4) for t, _ in res["story"]], "chained_seconds_all": [round(t, 4) for t, _ in res["chained"]],
+           "story_seconds_per_frame": res["story"][-1][1], "chained_seconds_per_frame": res["chained"][-1][1],
+           "story_split_seconds_synchronised": {k: round(v, 4) for k, v in split.items()}, "story_split_total": round(total, 4),
+           "first_story_seconds_incl_sampler_construction": round(first_story_s, 2), "samplers_cached": len(pipe._samplers),
+           "device_bytes_held_after_first_story": int(held), "device_bytes_grown_per_frame_of_first_story": grown[:K], "device_peak_bytes": int(torch.cuda.max_memory_allocated())}
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
