@@ -274,9 +274,12 @@ int sg_ff_geglu_fused_f16(const sg_ff_desc* d, sg_stream_t stream);
  * V is passed TRANSPOSED: vt[kb][h*D + d][j], keys contiguous (row stride ldvt, batch stride bsvt) — the host gets it
  * for free by running the V projection with swapped operands (VT = Wv . X^T).  Every vt row must hold finite values
  * up to Nk rounded up to a multiple of 8 (ldvt >= that).
+ * The kernels address one 64-key tile of K and one head slab of V^T with 32-bit element offsets: D * ldvt < 2^31 and 64 * ldk < 2^31
+ * (SG_EINVAL otherwise); Nq, Nk <= 2^30 and fewer than 2^31 workgroups.  scale must be finite and > 0 (SG_EINVAL otherwise): the
+ * row maximum is taken before the multiplication.
  * kv_batches: 0 or B = one K/V per query batch; 0 < kv_batches < B: query batch b reads K/V batch
  * (b < kv_batches ? b : b - (B - kv_batches)) — the image-conditioned CFG branches of the main pass share one
- * context.  Strides in elements: token stride ld*, batch stride bs*.
+ * context; 2 kv_batches >= B, so that the row index is never negative (SG_EINVAL otherwise).  Strides in elements: token stride ld*, batch stride bs*.
  */
 typedef struct sg_attn_desc {
     const sg_half* q;  int64_t ldq, bsq;
@@ -303,6 +306,33 @@ int sg_attn_fwd_f16(const sg_attn_desc* d, sg_stream_t stream);
  * depends on the other, so their workgroups share a grid (the short text problem fills the tail of the long image one).  Results
  * are bit-identical to two sg_attn_fwd_f16 calls.  Descriptors of different geometry are accepted and run as two launches. */
 int sg_attn_fwd_pair_f16(const sg_attn_desc* d0, const sg_attn_desc* d1, sg_stream_t stream);
+
+/* The launch a descriptor gets (host-only, nothing is launched; the launches choose through the same function): the kernel family, waves
+ * per workgroup, ring stages and workgroups.  Each wave owns 32 queries, except in the key-split family, where the waves of a workgroup
+ * share 32 queries.  sg_attn_fwd_plan validates the descriptor exactly as the launch does; lse != 0 plans sg_attn_fwd_lse_f16.
+ * Development options (sg_debug_set_option) are part of the answer. */
+enum {
+    SG_ATTN_D40_LOOP    = 0,   /* D = 40: tile 0 / steady state / drain loop (attn_d40_kernel, attn_d40_pair_kernel) */
+    SG_ATTN_SHARED_BODY = 1,   /* D = 40 fast path on the shared tile loop (option attn_d40_loop = 1) */
+    SG_ATTN_GENERAL     = 2,   /* general softmax, query-split: D = 80, D = 160, D = 40 under option attn_d40_general */
+    SG_ATTN_LEAN        = 3,   /* D = 40 fast path with V^T fragments per k-step (option attn_lean) */
+    SG_ATTN_KSPLIT      = 4,   /* D = 160, the waves split the keys of one 32-query block (stages = 1) */
+    SG_ATTN_LSE         = 5,   /* training forward: general softmax with the log-sum-exp rows stored */
+    SG_ATTN_F8          = 6    /* sg_attn_fwd_f8_d40 */
+};
+typedef struct sg_attn_plan {
+    int32_t family, waves, stages, workgroups;
+} sg_attn_plan;
+/* sg_attn_fwd_pair_f16(d0, d1): shared = 1 when one grid serves both problems — then first = the problem numbered first in it (the one
+ * with more keys; 0 on a tie), p0 / p1 = each problem's part of the grid and workgroups = the whole grid.  shared = 0: two launches,
+ * p0 / p1 as sg_attn_fwd_plan gives them, first = workgroups = 0. */
+typedef struct sg_attn_pair_plan {
+    int32_t shared, first;
+    sg_attn_plan p0, p1;
+    int32_t workgroups;
+} sg_attn_pair_plan;
+int sg_attn_fwd_plan(const sg_attn_desc* d, int32_t lse, sg_attn_plan* out);
+int sg_attn_fwd_pair_plan(const sg_attn_desc* d0, const sg_attn_desc* d1, sg_attn_pair_plan* out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * GroupNorm (+ optional SiLU) over NHWC fp16, fp32 statistics.
@@ -397,6 +427,9 @@ int sg_attn_f8_pack(const sg_half* src, int64_t ld, int64_t bs, void* dst, int32
                     sg_stream_t stream);
 int sg_attn_fwd_f8_d40(const void* q8, const void* k8, const void* vt8, sg_half* o, int64_t ldo, int64_t bso, int32_t B, int32_t H,
                        int32_t Nq, int32_t Nk, int32_t kv_batches, float scale, sg_stream_t stream);
+/* The launch shape sg_attn_fwd_f8_d40 uses for (B, H, Nq) (host-only): family SG_ATTN_F8, 2 or 4 waves, 3 stages.  sg_attn_fwd_f8_d40 also
+ * requires scale finite and > 0 and Nq, Nk <= 2^30. */
+int sg_attn_fwd_f8_plan(int32_t B, int32_t H, int32_t Nq, sg_attn_plan* out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Sampling-loop elementwise steps (model/pipeline.py:412-461), all fp32 NCHW [*,C,H,W] with `n` = elements per

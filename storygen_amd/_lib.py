@@ -109,6 +109,14 @@ class AttnDesc(C.Structure):
     ]
 
 
+class AttnPlan(C.Structure):
+    _fields_ = [("family", C.c_int32), ("waves", C.c_int32), ("stages", C.c_int32), ("workgroups", C.c_int32)]
+
+
+class AttnPairPlan(C.Structure):
+    _fields_ = [("shared", C.c_int32), ("first", C.c_int32), ("p0", AttnPlan), ("p1", AttnPlan), ("workgroups", C.c_int32)]
+
+
 class FfDesc(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("ldx", C.c_int64),
@@ -179,6 +187,9 @@ SIGNATURES = {
                                   C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sg_attn_fwd_f16": (C.c_int, [C.POINTER(AttnDesc), C.c_void_p]),
     "sg_attn_fwd_pair_f16": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnDesc), C.c_void_p]),
+    "sg_attn_fwd_plan": (C.c_int, [C.POINTER(AttnDesc), C.c_int32, C.POINTER(AttnPlan)]),
+    "sg_attn_fwd_pair_plan": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnDesc), C.POINTER(AttnPairPlan)]),
+    "sg_attn_fwd_f8_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(AttnPlan)]),
     "sg_groupnorm_nhwc_f16": (C.c_int, [C.POINTER(GroupNormDesc), C.c_void_p]),
     "sg_groupnorm_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "sg_layernorm_f16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,

@@ -26,6 +26,7 @@
 // LDS images (LDS-DMA, 1 KiB segments of 16 rows x 64 B): 16-byte slot c of row r is stored at slot c ^ ((r >> 2) & 3) —
 // 16 consecutive rows read the same logical slot conflict-free (4 rows per 256-byte bank row x 4 distinct slots).
 #include "common.h"
+#include <float.h>
 
 namespace {
 
@@ -310,12 +311,36 @@ extern "C" int sg_attn_f8_pack(const sg_half* src, int64_t ld, int64_t bs, void*
     return SG_OK;
 }
 
+// The launch shape of sg_attn_fwd_f8_d40: 4 waves where that still gives the chip >= 2 workgroups per CU, else 2; both on a 3-deep ring.
+static int attn_f8_plan(int32_t B, int32_t H, int32_t Nq, sg_attn_plan& pl, const char* who) {
+    SG_REQUIRE(B > 0 && H > 0 && Nq > 0, "%s: bad arguments", who);
+    const int waves = (int64_t)sg_cdiv(Nq, 128) * H * B >= 512 ? 4 : 2;
+    const int64_t wgs = (int64_t)sg_cdiv(Nq, 32 * waves) * H * B;
+    SG_REQUIRE(wgs < (1ll << 31), "%s: %lld workgroups do not fit a grid", who, (long long)wgs);
+    pl.family = SG_ATTN_F8; pl.waves = waves; pl.stages = 3; pl.workgroups = (int32_t)wgs;
+    return SG_OK;
+}
+
+extern "C" int sg_attn_fwd_f8_plan(int32_t B, int32_t H, int32_t Nq, sg_attn_plan* out) {
+    SG_REQUIRE(out != nullptr, "sg_attn_fwd_f8_plan: null plan");
+    return attn_f8_plan(B, H, Nq, *out, "sg_attn_fwd_f8_plan");
+}
+
+// 32-bit arithmetic of attn_fwd_f8_kernel / attn_f8_pack_kernel: key and query indices rounded up to a tile (tile * 64 + row, (tile + 1) * 64,
+// (qb NW + wave) * 32, Nkp = Nk rounded up to 64) stay below N + 128 — the check Nq, Nk <= 2^30 —, the grid is planned in 64 bits and checked
+// (attn_f8_plan); every offset into an image (row * 64, row * Nkp, (b H + h) * N * 64) is computed in `long`.
 extern "C" int sg_attn_fwd_f8_d40(const void* q8, const void* k8, const void* vt8, sg_half* o, int64_t ldo, int64_t bso, int32_t B,
                                   int32_t H, int32_t Nq, int32_t Nk, int32_t kv_batches, float scale, sg_stream_t stream) {
     SG_REQUIRE(q8 && k8 && vt8 && o && B > 0 && H > 0 && Nq > 0 && Nk > 0, "sg_attn_fwd_f8_d40: bad arguments");
+    SG_REQUIRE(Nq <= (1 << 30) && Nk <= (1 << 30), "sg_attn_fwd_f8_d40: Nq and Nk must not exceed 2^30");
+    // (the row maximum is taken of the raw scores and the key tail masked with -inf before the multiplication: see attention.hip)
+    SG_REQUIRE(scale > 0.f && scale <= FLT_MAX, "sg_attn_fwd_f8_d40: scale must be finite and > 0");
     SG_REQUIRE(kv_batches >= 0 && kv_batches <= B, "sg_attn_fwd_f8_d40: kv_batches must be in [0, B]");
+    SG_REQUIRE(kv_batches == 0 || 2 * (int64_t)kv_batches >= B, "sg_attn_fwd_f8_d40: kv_batches must be 0 or at least B / 2");
     SG_REQUIRE(sg_aligned16(q8) && sg_aligned16(k8) && sg_aligned16(vt8) && (reinterpret_cast<uintptr_t>(o) & 7u) == 0 && ldo % 4 == 0 &&
                bso % 4 == 0 && ldo >= (int64_t)H * 40, "sg_attn_fwd_f8_d40: alignment / strides");
+    sg_attn_plan pl;
+    if (int rc = attn_f8_plan(B, H, Nq, pl, "sg_attn_fwd_f8_d40")) return rc;
     F8Params p{};
     p.q8 = reinterpret_cast<const unsigned char*>(q8);
     p.k8 = reinterpret_cast<const unsigned char*>(k8);
@@ -324,14 +349,9 @@ extern "C" int sg_attn_fwd_f8_d40(const void* q8, const void* k8, const void* vt
     p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.Nkp = (Nk + 63) & ~63;
     p.kv_batches = kv_batches > 0 ? kv_batches : B;
     p.scale_log2 = scale * 1.44269504088896340736f;
-    const long wgs4 = (long)sg_cdiv(Nq, 128) * H * B;
-    if (wgs4 >= 512) {
-        p.nqb = sg_cdiv(Nq, 128);
-        hipLaunchKernelGGL((attn_fwd_f8_kernel<4, 3>), dim3(p.nqb * H * B), dim3(256), 0, (hipStream_t)stream, p);
-    } else {
-        p.nqb = sg_cdiv(Nq, 64);
-        hipLaunchKernelGGL((attn_fwd_f8_kernel<2, 3>), dim3(p.nqb * H * B), dim3(128), 0, (hipStream_t)stream, p);
-    }
+    p.nqb = sg_cdiv(Nq, 32 * pl.waves);
+    if (pl.waves == 4) hipLaunchKernelGGL((attn_fwd_f8_kernel<4, 3>), dim3(pl.workgroups), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((attn_fwd_f8_kernel<2, 3>), dim3(pl.workgroups), dim3(128), 0, (hipStream_t)stream, p);
     SG_CHECK_LAUNCH("sg_attn_fwd_f8_d40");
     return SG_OK;
 }

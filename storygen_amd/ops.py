@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, ConvDesc, FfDesc, GemmDesc, GroupNormDesc, check
+from ._lib import AttnDesc, AttnPairPlan, AttnPlan, ConvDesc, FfDesc, GemmDesc, GroupNormDesc, check
 
 lib = _lib.load()
 
@@ -552,12 +552,47 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Ten
 
 
 def attention_pair(a: tuple, b: tuple, heads: int, scale: float) -> None:
-    """Two attentions of the same query geometry in one launch (sg_attn_fwd_pair_f16): a, b = (q, k, vt, out, nk) as in attention()
-    — the text and the image cross-attention of one transformer block (attention.py:271-276,285-290)."""
-    da, fa, sa = _attn_fwd_desc(a[0], a[1], a[2], a[3], heads, scale, a[4])
-    db, fb, sb = _attn_fwd_desc(b[0], b[1], b[2], b[3], heads, scale, b[4])
+    """Two attentions of the same query geometry in one launch (sg_attn_fwd_pair_f16): a, b = (q, k, vt, out, nk[, short]) as in
+    attention() — the text and the image cross-attention of one transformer block (attention.py:271-276,285-290)."""
+    da, fa, sa = _attn_fwd_desc(*a[:4], heads, scale, *a[4:])
+    db, fb, sb = _attn_fwd_desc(*b[:4], heads, scale, *b[4:])
     with _timed(f"attention_d{da.D}", fa + fb, f"{sa} + {sb}"):
         check(lib.sg_attn_fwd_pair_f16(C.byref(da), C.byref(db), _stream()), "sg_attn_fwd_pair_f16")
+
+
+# kernel families of a forward-attention plan (SG_ATTN_* of include/storygen_hip.h, in that order)
+ATTN_FAMILIES = ("d40_loop", "shared_body", "general", "lean", "ksplit", "lse", "f8")
+
+
+def _attn_plan_tuple(pl) -> tuple:
+    return (ATTN_FAMILIES[pl.family], pl.waves, pl.stages, pl.workgroups)
+
+
+def attention_plan(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, heads: int, scale: float,
+                   nk: Optional[int] = None, short: Optional[tuple] = None, lse: bool = False) -> tuple:
+    """The launch an attention() call (lse=True: attention_lse()) with these arguments gets (sg_attn_fwd_plan; no launch):
+    (family, waves per workgroup, ring stages, workgroups), family one of ATTN_FAMILIES."""
+    d, _, _ = _attn_fwd_desc(q, k, vt, out, heads, scale, nk, short)
+    pl = AttnPlan()
+    check(lib.sg_attn_fwd_plan(C.byref(d), int(lse), C.byref(pl)), "sg_attn_fwd_plan")
+    return _attn_plan_tuple(pl)
+
+
+def attention_pair_plan(a: tuple, b: tuple, heads: int, scale: float) -> tuple:
+    """The launch(es) an attention_pair() call with these arguments gets (sg_attn_fwd_pair_plan; no launch): (one grid serves both,
+    index of the problem numbered first in it, plan of a, plan of b, workgroups of the shared grid or 0)."""
+    da, _, _ = _attn_fwd_desc(*a[:4], heads, scale, *a[4:])
+    db, _, _ = _attn_fwd_desc(*b[:4], heads, scale, *b[4:])
+    pr = AttnPairPlan()
+    check(lib.sg_attn_fwd_pair_plan(C.byref(da), C.byref(db), C.byref(pr)), "sg_attn_fwd_pair_plan")
+    return (bool(pr.shared), pr.first, _attn_plan_tuple(pr.p0), _attn_plan_tuple(pr.p1), pr.workgroups)
+
+
+def attention_f8_plan(B: int, heads: int, Nq: int) -> tuple:
+    """The launch shape attention_f8() uses for these queries (sg_attn_fwd_f8_plan; no launch): as attention_plan."""
+    pl = AttnPlan()
+    check(lib.sg_attn_fwd_f8_plan(B, heads, Nq, C.byref(pl)), "sg_attn_fwd_f8_plan")
+    return _attn_plan_tuple(pl)
 
 
 def attention_f8_bytes(B: int, heads: int, N: int, transposed: bool) -> int:

@@ -66,7 +66,8 @@ def test_descriptor_layouts_match_a_c_compiler(tmp_path):
     from storygen_amd import _lib
     structs = {"sg_gemm_desc": _lib.GemmDesc, "sg_conv3x3_desc": _lib.ConvDesc, "sg_attn_desc": _lib.AttnDesc,
                "sg_groupnorm_desc": _lib.GroupNormDesc, "sg_groupnorm_bwd_desc": _lib.GroupNormBwdDesc,
-               "sg_attn_bwd_desc": _lib.AttnBwdDesc, "sg_adamw_desc": _lib.AdamWDesc}
+               "sg_attn_bwd_desc": _lib.AttnBwdDesc, "sg_adamw_desc": _lib.AdamWDesc,
+               "sg_attn_plan": _lib.AttnPlan, "sg_attn_pair_plan": _lib.AttnPairPlan}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
     for cname, st in structs.items():
         lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
@@ -194,6 +195,117 @@ def test_launch_plans_match_the_recording(lib):
         for rg, rw in zip(g["rows"], w["rows"]):
             assert rg == rw, (g["options"], rw, rg)
     assert sum(len(s["rows"]) for s in want) == 1436
+
+
+def _attn_desc(B=1, H=8, Nq=64, Nk=64, D=40, scale=None, **kw):
+    from storygen_amd._lib import AttnDesc
+    a = AttnDesc()
+    a.q, a.k, a.vt, a.o = 0x10000, 0x20000, 0x30000, 0x40000
+    a.B, a.H, a.Nq, a.Nk, a.D = B, H, Nq, Nk, D
+    a.ldq = a.ldk = a.ldo = H * D
+    a.ldvt = (Nk + 7) & ~7
+    a.scale = D ** -0.5 if scale is None else scale
+    for n, v in kw.items():
+        setattr(a, n, v)
+    return a
+
+
+def test_attention_scale_and_k_tile_bound_are_rejected_on_the_host(lib):
+    """No launch: scale must be finite and > 0 (the general softmax takes the row maximum of the raw scores and masks the key tail with
+    -inf before multiplying: scale < 0 would select the minimum, scale = 0 give 0 * -inf), and one 64-key tile of K must fit 32-bit
+    element offsets, 64 ldk < 2^31, like D ldvt < 2^31 on the V^T side.  Both through the plan query and through the launch entry
+    points; descriptors on fake pointers, nothing near 4 GiB is allocated."""
+    from storygen_amd._lib import AttnPairPlan, AttnPlan
+    pl, pr = AttnPlan(), AttnPairPlan()
+    good = _attn_desc()
+    assert lib.sg_attn_fwd_plan(C.byref(good), 0, C.byref(pl)) == 0
+    for D in (40, 80, 160):
+        for scale in (0.0, -0.125, float("inf"), float("-inf"), float("nan")):
+            a = _attn_desc(D=D, scale=scale)
+            for lse in (0, 1):
+                assert lib.sg_attn_fwd_plan(C.byref(a), lse, C.byref(pl)) == -1 and b"scale must be finite and > 0" in lib.sg_last_error()
+            assert lib.sg_attn_fwd_f16(C.byref(a), None) == -1 and b"scale must be finite and > 0" in lib.sg_last_error()
+            assert lib.sg_attn_fwd_lse_f16(C.byref(a), 0x50000, None) == -1 and b"scale" in lib.sg_last_error()
+            for d0, d1 in ((a, good), (good, a)):
+                assert lib.sg_attn_fwd_pair_plan(C.byref(d0), C.byref(d1), C.byref(pr)) == -1 and b"scale" in lib.sg_last_error()
+                assert lib.sg_attn_fwd_pair_f16(C.byref(d0), C.byref(d1), None) == -1 and b"scale" in lib.sg_last_error()
+            if D == 40:
+                assert lib.sg_attn_fwd_f8_d40(0x10000, 0x20000, 0x30000, 0x40000, 320, 320 * 64, 1, 8, 64, 64, 0, scale, None) == -1
+                assert b"scale must be finite and > 0" in lib.sg_last_error()
+        # 64 ldk < 2^31: ldk = 2^25 - 8 is the last accepted token stride
+        ok, bad = _attn_desc(D=D, ldk=2 ** 25 - 8), _attn_desc(D=D, ldk=2 ** 25)
+        assert lib.sg_attn_fwd_plan(C.byref(ok), 0, C.byref(pl)) == 0
+        assert lib.sg_attn_fwd_plan(C.byref(bad), 0, C.byref(pl)) == -1 and b"64 ldk" in lib.sg_last_error()
+        assert lib.sg_attn_fwd_f16(C.byref(bad), None) == -1 and b"64 ldk" in lib.sg_last_error()
+        assert lib.sg_attn_fwd_pair_f16(C.byref(good if D == 40 else ok), C.byref(bad), None) == -1 and b"64 ldk" in lib.sg_last_error()
+        # the V^T rule beside it: D ldvt < 2^31
+        assert lib.sg_attn_fwd_plan(C.byref(_attn_desc(D=D, ldvt=(2 ** 31 // D - 8) & ~7)), 0, C.byref(pl)) == 0
+        assert lib.sg_attn_fwd_plan(C.byref(_attn_desc(D=D, ldvt=(2 ** 31 // D + 8) & ~7)), 0, C.byref(pl)) == -1 and b"VT head slab" in lib.sg_last_error()
+    # query batch b >= kv_batches reads K/V row b - (B - kv_batches): B 5 on 2 rows would read row -1
+    assert lib.sg_attn_fwd_plan(C.byref(_attn_desc(B=5, kv_batches=3)), 0, C.byref(pl)) == 0
+    assert lib.sg_attn_fwd_plan(C.byref(_attn_desc(B=5, kv_batches=2)), 0, C.byref(pl)) == -1 and b"at least B / 2" in lib.sg_last_error()
+    assert lib.sg_attn_fwd_f16(C.byref(_attn_desc(B=5, kv_batches=2)), None) == -1 and b"at least B / 2" in lib.sg_last_error()
+    assert lib.sg_attn_fwd_f8_d40(0x10000, 0x20000, 0x30000, 0x40000, 320, 320 * 64, 5, 8, 64, 64, 2, 0.158, None) == -1 and b"at least B / 2" in lib.sg_last_error()
+    assert lib.sg_attn_fwd_plan(C.byref(_attn_desc(Nk=2 ** 30 + 8, ldvt=2 ** 30 + 8)), 0, C.byref(pl)) == -1 and b"2^30" in lib.sg_last_error()
+
+
+def test_attention_launch_plans_on_the_host(lib):
+    """sg_attn_fwd_plan / sg_attn_fwd_pair_plan / sg_attn_fwd_f8_plan at both sides of every dispatch threshold, and under the development
+    options (no launch): (family, waves, stages, workgroups)."""
+    from storygen_amd._lib import AttnPairPlan, AttnPlan
+    D40, SHARED, GENERAL, LEAN, KSPLIT, LSE, F8 = range(7)
+
+    def plan(lse=0, **kw):
+        pl = AttnPlan()
+        assert lib.sg_attn_fwd_plan(C.byref(_attn_desc(**kw)), lse, C.byref(pl)) == 0, lib.sg_last_error()
+        return (pl.family, pl.waves, pl.stages, pl.workgroups)
+
+    # D = 40: cdiv(Nq, 128) H B >= 512 -> 4 waves x 3 stages
+    assert plan(B=16, Nq=512) == (D40, 4, 3, 512) and plan(B=16, Nq=384) == (D40, 2, 2, 768) and plan(B=16, Nq=390) == (D40, 4, 3, 512)
+    # D = 160: key split at Nq <= 256, Nk > 64 and cdiv(Nq, 32) H B <= 256
+    assert plan(D=160, B=4, Nq=256, Nk=65) == (KSPLIT, 4, 1, 256) and plan(D=160, B=4, Nq=256, Nk=64) == (GENERAL, 4, 3, 64)
+    assert plan(D=160, B=5, Nq=256, Nk=65) == (GENERAL, 4, 3, 80) and plan(D=160, B=1, Nq=257, Nk=65) == (GENERAL, 4, 3, 24)
+    assert plan(D=160, B=20, Nq=256, Nk=256) == (GENERAL, 4, 3, 320)
+    assert plan(D=160, B=1, H=3, Nq=7, Nk=577) == (KSPLIT, 4, 1, 3)
+    assert plan(D=80, B=1, Nq=64, Nk=640) == (GENERAL, 4, 3, 8)
+    for D in (40, 80, 160):
+        assert plan(lse=1, D=D, B=2, Nq=130, Nk=65) == (LSE, 4, 3, 2 * 8 * 2)
+    try:
+        lib.sg_debug_set_option(b"attn_d160", 3)
+        assert plan(D=160, B=4, Nq=256, Nk=65) == (GENERAL, 4, 3, 64)
+        lib.sg_debug_set_option(b"reset", 0)
+        lib.sg_debug_set_option(b"attn_d40_loop", 1)
+        assert plan(B=16, Nq=512) == (SHARED, 4, 3, 512) and plan(B=1, Nq=64) == (SHARED, 2, 2, 8)
+        lib.sg_debug_set_option(b"reset", 0)
+        lib.sg_debug_set_option(b"attn_lean", 1)
+        assert plan(B=16, Nq=512) == (LEAN, 4, 3, 512) and plan(B=1, Nq=64) == (D40, 2, 2, 8)
+        lib.sg_debug_set_option(b"attn_d40_general", 1)
+        assert plan(B=16, Nq=512) == (GENERAL, 4, 3, 512) and plan(B=1, Nq=64) == (D40, 2, 2, 8)
+    finally:
+        lib.sg_debug_set_option(b"reset", 0)
+
+    def pair(a, b):
+        pr = AttnPairPlan()
+        assert lib.sg_attn_fwd_pair_plan(C.byref(_attn_desc(**a)), C.byref(_attn_desc(**b)), C.byref(pr)) == 0, lib.sg_last_error()
+        return (pr.shared, pr.first, (pr.p0.family, pr.p0.waves, pr.p0.stages, pr.p0.workgroups),
+                (pr.p1.family, pr.p1.waves, pr.p1.stages, pr.p1.workgroups), pr.workgroups)
+
+    assert pair(dict(B=3, H=3, Nq=200, Nk=77), dict(B=3, H=3, Nq=200, Nk=130)) == (1, 1, (D40, 2, 2, 36), (D40, 2, 2, 36), 72)
+    assert pair(dict(B=3, H=3, Nq=200, Nk=77), dict(B=3, H=3, Nq=200, Nk=77))[:2] == (1, 0)
+    assert pair(dict(B=16, Nq=512, Nk=77), dict(B=16, Nq=512, Nk=64)) == (1, 0, (D40, 4, 3, 512), (D40, 4, 3, 512), 1024)
+    # D = 160: the shared grid runs the query-split kernel also where the single launches would split the keys
+    assert pair(dict(D=160, B=3, Nq=64, Nk=192), dict(D=160, B=3, Nq=64, Nk=77)) == (1, 0, (GENERAL, 4, 3, 24), (GENERAL, 4, 3, 24), 48)
+    assert pair(dict(D=160, B=3, Nq=64, Nk=192), dict(D=160, B=3, Nq=32, Nk=77)) == (0, 0, (KSPLIT, 4, 1, 48), (KSPLIT, 4, 1, 24), 0)
+    assert pair(dict(D=80, B=2, Nq=130, Nk=65), dict(D=80, B=2, Nq=130, Nk=320)) == (1, 1, (GENERAL, 4, 3, 32), (GENERAL, 4, 3, 32), 64)
+    try:
+        lib.sg_debug_set_option(b"attn_d40_loop", 1)
+        assert pair(dict(B=3, Nq=200, Nk=77), dict(B=3, Nq=200, Nk=130)) == (0, 0, (SHARED, 2, 2, 96), (SHARED, 2, 2, 96), 0)
+    finally:
+        lib.sg_debug_set_option(b"reset", 0)
+    pl = AttnPlan()
+    assert lib.sg_attn_fwd_f8_plan(16, 8, 512, C.byref(pl)) == 0 and (pl.family, pl.waves, pl.stages, pl.workgroups) == (F8, 4, 3, 512)
+    assert lib.sg_attn_fwd_f8_plan(16, 8, 384, C.byref(pl)) == 0 and (pl.family, pl.waves, pl.stages, pl.workgroups) == (F8, 2, 3, 768)
+    assert lib.sg_attn_fwd_f8_plan(0, 8, 384, C.byref(pl)) == -1
 
 
 def test_backward_entry_points_validate_on_the_host(lib):

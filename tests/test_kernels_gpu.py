@@ -973,7 +973,8 @@ ATTN_CASES = [
     (2, 8, 256, 256, 40), (1, 8, 200, 77, 40), (3, 8, 64, 192, 160), (2, 8, 256, 768, 80), (1, 8, 1024, 1024, 80),
     (1, 2, 130, 65, 160), (3, 8, 4096, 77, 40), (1, 8, 1024, 3072, 40), (1, 4, 33, 1, 80),
     (2, 8, 4096, 705, 40), (2, 8, 4096, 320, 40),      # big grids: the 4-wave kernels, ragged last tile / odd tile count
-    # D = 160 at Nq <= 256: the key-split workgroups (round 5) — 12 / 4 / 2 / 1 tiles for 4 waves, ragged queries and keys, many batches
+    # D = 160 at Nq <= 256: the key-split workgroups (round 5) — 12 / 4 / 2 tiles for 4 waves, ragged queries and keys; (20, 8, 256, 256) has
+    # 1 280 workgroups of 32 queries, more than the 256 the key split is chosen for, and (2, 8, 64, 64) a single tile: both run the query-split kernel
     (3, 8, 256, 768, 160), (3, 8, 256, 256, 160), (3, 8, 256, 77, 160), (1, 8, 250, 330, 160), (20, 8, 256, 256, 160), (2, 8, 64, 64, 160),
 ]
 
