@@ -505,6 +505,51 @@ int sg_pad_cast_f16(const void* x, int64_t ldx, int32_t x_f32, sg_half* y, int64
 int sg_frame_handoff_f16(const sg_half* x, int64_t bsx, int64_t csx, int64_t ldx, uint8_t* u8, int64_t bsu, int64_t ldu,
                          sg_half* y, int64_t bsy, int64_t csy, int64_t ldy, int32_t N, int32_t H, int32_t W, sg_stream_t stream);
 
+/* Image ingest: Pillow's `Image.resize(size)` on 8-bit images (its default bicubic filter, a = -0.5) followed by ToTensor, bit for bit, in
+ * one launch — the chain every reference frame, training image and mask goes through (inference.py:84-89, dataset.py:37-43).  Pillow's
+ * resize is no float bicubic: it is two fixed-point passes, horizontal first, with a rounding and clip to uint8 between them.
+ *
+ * Per axis (`in` -> `out` samples), all in double without fused multiply-adds:
+ *   scale = in / out;  fs = max(scale, 1);  support = 2 fs;  ksize = 2 (int)ceil(support) + 1
+ *   output sample xx:  center = (xx + 0.5) scale;  xmin = max((int)(center - support + 0.5), 0);
+ *                      n = min((int)(center + support + 0.5), in) - xmin
+ *                      w[x] = bicubic((x + xmin - center + 0.5) / fs), x < n;  w[x] /= sum (in index order, when it is not 0)
+ *                      k[x] = (int)(w[x] 2^22 -+ 0.5) (C truncation; - for w[x] < 0), 0 for x >= n
+ *   out[xx] = clamp((2^21 + sum_{x < n} in[xmin + x] k[x]) >> 22, 0, 255)      int32 (sum |k| 255 + 2^21 < 2^31 at every admitted
+ *                                                                              ratio), arithmetic shift
+ * A pass whose in == out is skipped, as Pillow skips it; channels are independent.
+ *
+ * sg_image_resample_ksize(in, out): ksize of one axis.
+ * sg_image_resample_table(in, out, coef, bounds): fills HOST buffers coef int32 [out, ksize] and bounds int32 [out, 2] = (xmin, n).  No
+ *   device is touched; the caller uploads the tables (the library owns no device memory).
+ * sg_image_resize_u8: x uint8 [N, Hin, Win, C], C = 1 or 3 (batch / row strides bsx / ldx in bytes, pixels contiguous in a row) ->
+ *   u8: uint8 [N, Hout, Wout, C] (bsu / ldu), the image as Pillow returns it;
+ *   y:  fp16 [N, C, Hout, Wout] (bsy / csy / ldy in elements, unit pixel stride), fp16(fp32(u8) / 255): ToTensor and the pipeline's cast.
+ *   Either output may be NULL, not both.  flip = 1 mirrors the output columns (RandomHorizontalFlip after the resize, as the datasets
+ *   apply it).  hcoef / hbounds, vcoef / vbounds: DEVICE copies of the tables of (Win, Wout) and (Hin, Hout); both NULL for a skipped
+ *   pass.  The kernel forces xmin and n inside the input extent and n inside ksize: a wrong table gives wrong pixels, never a read
+ *   outside x.  No alignment is required and nothing outside the output windows is written.
+ *   A workgroup owns SG_IMAGE_TILE_W output columns x up to SG_IMAGE_TILE_H output rows: it runs the horizontal pass of the input rows
+ *   its vertical taps read into LDS as uint8, then the vertical pass out of LDS; no workspace.  sg_image_resize_tile_rows(Hin, Hout, C)
+ *   is the number of output rows per tile the launch uses: the largest <= SG_IMAGE_TILE_H whose LDS image fits SG_IMAGE_LDS_BYTES (two
+ *   workgroups per CU).
+ * Limits: sides 1 .. SG_IMAGE_MAX_SIDE, in <= SG_IMAGE_MAX_RATIO * out on each axis (ksize <= SG_IMAGE_MAX_KSIZE), N <= 65535.
+ * SG_EINVAL before any launch: a null input or two null outputs, sizes <= 0 or above the limits, C outside {1, 3}, flip outside {0, 1},
+ * strides that make a tensor overlap itself, outputs that overlap each other or the input, a table missing for a pass that runs or given
+ * for one that is skipped. */
+#define SG_IMAGE_MAX_SIDE 16384
+#define SG_IMAGE_MAX_RATIO 32
+#define SG_IMAGE_MAX_KSIZE 129
+#define SG_IMAGE_TILE_W 64
+#define SG_IMAGE_TILE_H 16
+#define SG_IMAGE_LDS_BYTES 65536
+int sg_image_resample_ksize(int32_t in, int32_t out);
+int sg_image_resample_table(int32_t in, int32_t out, int32_t* coef, int32_t* bounds);
+int sg_image_resize_tile_rows(int32_t in_h, int32_t out_h, int32_t C);
+int sg_image_resize_u8(const uint8_t* x, int64_t bsx, int64_t ldx, int32_t N, int32_t Hin, int32_t Win, int32_t C, uint8_t* u8, int64_t bsu,
+                       int64_t ldu, sg_half* y, int64_t bsy, int64_t csy, int64_t ldy, int32_t Hout, int32_t Wout, const int32_t* hcoef,
+                       const int32_t* hbounds, const int32_t* vcoef, const int32_t* vbounds, int32_t flip, sg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * The networks either side of the loop: CLIP text encoder and AutoencoderKL.  Their GEMMs, convolutions,
  * GroupNorms and LayerNorms are the entry points above; these are the remaining pieces.

@@ -212,6 +212,12 @@ SIGNATURES = {
                                   C.c_int32, C.c_void_p]),
     "sg_frame_handoff_f16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                        C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sg_image_resample_ksize": (C.c_int, [C.c_int32, C.c_int32]),
+    "sg_image_resample_table": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sg_image_resize_tile_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "sg_image_resize_u8": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                     C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "sg_attn_f8_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "sg_attn_f8_pack": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sg_attn_fwd_f8_d40": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,

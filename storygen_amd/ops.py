@@ -1020,6 +1020,77 @@ def frame_handoff(x: torch.Tensor, out_u8: Optional[torch.Tensor] = None, out_f1
     return out_u8, out_f16
 
 
+# SG_IMAGE_*: limits and tile of sg_image_resize_u8 (include/storygen_hip.h)
+IMAGE_MAX_SIDE, IMAGE_MAX_RATIO, IMAGE_MAX_KSIZE, IMAGE_TILE_W, IMAGE_TILE_H, IMAGE_LDS_BYTES = 16384, 32, 129, 64, 16, 65536
+_image_tables = {}       # (in, out, device) -> (coef int32 [out, ksize], bounds int32 [out, 2]) on that device
+
+
+def image_resample_table(n_in: int, n_out: int):
+    """Pillow's fixed-point bicubic coefficients of one axis from the library's host builder (sg_image_resample_table), as CPU tensors:
+    (coef int32 [n_out, ksize], bounds int32 [n_out, 2] = (first input sample, taps))."""
+    ks = lib.sg_image_resample_ksize(n_in, n_out)
+    check(min(ks, 0), "sg_image_resample_ksize")
+    coef, bounds = torch.empty(n_out, ks, dtype=torch.int32), torch.empty(n_out, 2, dtype=torch.int32)
+    check(lib.sg_image_resample_table(n_in, n_out, coef.data_ptr(), bounds.data_ptr()), "sg_image_resample_table")
+    return coef, bounds
+
+
+def image_resize_tile_rows(h_in: int, h_out: int, channels: int) -> int:
+    """Output rows per workgroup tile that image_resize uses for this geometry (sg_image_resize_tile_rows)."""
+    th = lib.sg_image_resize_tile_rows(h_in, h_out, channels)
+    check(min(th, 0), "sg_image_resize_tile_rows")
+    return th
+
+
+def _image_table(n_in: int, n_out: int, device):
+    if n_in == n_out:
+        return None, None
+    key = (n_in, n_out, str(device))
+    if key not in _image_tables:
+        _image_tables[key] = tuple(t.to(device) for t in image_resample_table(n_in, n_out))
+    return _image_tables[key]
+
+
+def image_resize(x_u8: torch.Tensor, size, flip: bool = False, out_u8=None, out_f16=None):
+    """x_u8 uint8 [N,h,w,C], C = 1 or 3 (any batch / row stride, contiguous pixels) -> (uint8 [N,H,W,C]: Image.resize(size) of Pillow on
+    every image, bit for bit — its bicubic default, two 8-bit fixed-point passes; fp16 [N,C,H,W]: ToTensor of that, cast to fp16), in one
+    launch of sg_image_resize_u8.  size = (W, H), as Pillow's.  flip mirrors the columns after the resize.  Outputs are allocated when
+    None and may be windows of larger buffers; pass False for one that is not wanted (None comes back in its place).  The coefficient
+    tables come from the library's host builder and are kept on the device per (in, out) pair."""
+    if x_u8.dtype != torch.uint8 or not x_u8.is_cuda:
+        raise TypeError(f"x_u8: expected a CUDA/HIP uint8 tensor, got {x_u8.dtype} on {x_u8.device}")
+    if x_u8.dim() != 4 or x_u8.shape[3] not in (1, 3):
+        raise ValueError(f"image_resize: x_u8 must be [N,h,w,1] or [N,h,w,3], got {tuple(x_u8.shape)}")
+    N, h, w, Cc = x_u8.shape
+    W, H = (int(s) for s in size)
+    if out_u8 is False and out_f16 is False:
+        raise ValueError("image_resize: no output is wanted")
+    if H <= 0 or W <= 0:
+        raise ValueError(f"image_resize: size must be positive, got {(W, H)}")
+    if out_u8 is None:
+        out_u8 = torch.empty(N, H, W, Cc, dtype=torch.uint8, device=x_u8.device)
+    if out_f16 is None:
+        out_f16 = torch.empty(N, Cc, H, W, dtype=torch.float16, device=x_u8.device)
+    out_u8, out_f16 = (None if o is False else o for o in (out_u8, out_f16))
+    if out_u8 is not None:
+        if out_u8.dtype != torch.uint8 or not out_u8.is_cuda:
+            raise TypeError(f"out_u8: expected a CUDA/HIP uint8 tensor, got {out_u8.dtype} on {out_u8.device}")
+        if tuple(out_u8.shape) != (N, H, W, Cc):
+            raise ValueError(f"image_resize: out_u8 must be {(N, H, W, Cc)}, got {tuple(out_u8.shape)}")
+    if out_f16 is not None:
+        _f16(out_f16, "out_f16")
+        if tuple(out_f16.shape) != (N, Cc, H, W):
+            raise ValueError(f"image_resize: out_f16 must be {(N, Cc, H, W)}, got {tuple(out_f16.shape)}")
+    if any(t is not None and (t.stride(3) != 1 or t.stride(2) != Cc) for t in (x_u8, out_u8)) or (out_f16 is not None and out_f16.stride(3) != 1):
+        raise ValueError("image_resize: [.., w, C] contiguous pixels on x_u8 and out_u8, unit pixel stride on out_f16")
+    (hc, hb), (vc, vb) = _image_table(w, W, x_u8.device), _image_table(h, H, x_u8.device)      # (refuses sizes beyond the limits)
+    su = (out_u8.stride(0), out_u8.stride(1)) if out_u8 is not None else (0, 0)
+    sy = (out_f16.stride(0), out_f16.stride(1), out_f16.stride(2)) if out_f16 is not None else (0, 0, 0)
+    check(lib.sg_image_resize_u8(x_u8.data_ptr(), x_u8.stride(0), x_u8.stride(1), N, h, w, Cc, _p(out_u8), *su, _p(out_f16), *sy, H, W,
+                                 _p(hc), _p(hb), _p(vc), _p(vb), int(bool(flip)), _stream()), "sg_image_resize_u8")
+    return out_u8, out_f16
+
+
 # ------------------------------------------------------------------------------------------------ backward pass (config 4)
 # Validated on MI355X in round 2 (tests/test_backward_gpu.py).  Kernels: csrc/backward.hip, attention_bwd.hip; formulas: oracle/storygen_backward.py.
 def layernorm_bwd(x: torch.Tensor, dy1: torch.Tensor, g1: torch.Tensor, out: torch.Tensor, eps: float = 1e-5,

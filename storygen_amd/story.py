@@ -18,8 +18,11 @@ to the scorer and, once, at the end, to the host.  The frames are the ones the c
 Convention of the context frames: values in [0, 1].  inference.py:90-91 (`for ref_image in ref_images: ref_image = ref_image * 2. - 1.`)
 rebinds its loop variable, so the `* 2 - 1` never reaches the tensor the pipeline gets; that convention is kept, for `first_frames` too.
 
-Out of scope: reading / writing / resizing image files (the caller passes [K,3,H,W] tensors), multi-GPU stories (independent: the
-data-parallel launcher applies unchanged)."""
+First frames the caller brings may be raw 8-bit images of any size (PIL images, uint8 arrays, a uint8 [K,h,w,3] tensor): they are resized
+on the device exactly as Pillow's `.resize((width, height))` and ToTensor would (storygen_amd/image.py, sg_image_resize_u8).
+
+Out of scope: reading / writing / converting image files (the caller passes decoded RGB images or [K,3,H,W] tensors), multi-GPU stories
+(independent: the data-parallel launcher applies unchanged)."""
 from __future__ import annotations
 
 from collections import deque, namedtuple
@@ -52,11 +55,13 @@ class StoryGenerator:
 
     @torch.no_grad()
     def generate(self, prompts: List[str], *, context_frames: int = 3, stage: str = "auto-regressive", samples_per_frame: int = 1,
-                 first_frames: Optional[torch.Tensor] = None, first_prompts: Optional[List[str]] = None, num_inference_steps: int = 40,
+                 first_frames=None, first_prompts: Optional[List[str]] = None, num_inference_steps: int = 40,
                  guidance_scale: float = 7.0, image_guidance_scale: float = 3.5, eta: float = 0.0, generator=None, height: int = 512,
                  width: int = 512, output_type: str = "pil") -> StoryOutput:
         """One frame per prompt.  Frame j is one pipeline call conditioned on the last min(j + len(first_frames), context_frames) frames
-        of the story so far — the caller's `first_frames` ([K,3,H,W] in [0, 1], with `first_prompts`), then the kept generated frames —
+        of the story so far — the caller's `first_frames` (a float [K,3,H,W] tensor in [0, 1], or raw 8-bit images of any size: a list of
+        PIL images / uint8 [h,w,3] arrays or a uint8 [K,h,w,3] tensor, resized as Pillow's `.resize((width, height))` + ToTensor by
+        image.load_reference_images; with `first_prompts`), then the kept generated frames —
         oldest first, with their prompts as `prev_prompt` (the order of the reference's `ref_image` / `ref_prompt` lists).  A frame with
         no prior frame runs stage "no", the reference's text-only path; the call still wants one `image_prompt` frame and prompt
         (pipeline.py encodes them before the stage is looked at, and the sampler is sized for at least one): a zero frame and the
@@ -87,6 +92,9 @@ class StoryGenerator:
         dev = pipe.device
         ring = deque(maxlen=context_frames)              # (fp16 [3,H,W] on the device, prompt), oldest first
         if first_frames is not None:
+            if isinstance(first_frames, (list, tuple)) or (isinstance(first_frames, torch.Tensor) and first_frames.dtype == torch.uint8):
+                from .image import load_reference_images
+                first_frames = load_reference_images(first_frames, size=(width, height), device=dev)
             if first_frames.dim() != 4 or tuple(first_frames.shape[1:]) != (3, height, width) or not first_frames.is_floating_point():
                 raise ValueError(f"StoryGenerator.generate: first_frames must be a float [K,3,{height},{width}] tensor in [0, 1], got "
                                  f"{first_frames.dtype} {tuple(first_frames.shape)}")

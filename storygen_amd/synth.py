@@ -84,14 +84,14 @@ def synthetic_state_dict(arch: UNetArch, seed: int = 0, workers: int = 1) -> "Or
     return OrderedDict(zip(shapes, tensors))
 
 
-_shape_cache: Dict[int, "OrderedDict[str, tuple]"] = {}
+_shape_cache: Dict[int, tuple] = {}      # id(arch) -> (arch, shapes): the entry keeps its arch alive, so its id cannot pass to another one
 
 
 def param_shapes_cache(arch: UNetArch):
     k = id(arch)
-    if k not in _shape_cache:
-        _shape_cache[k] = param_shapes(arch)
-    return _shape_cache[k]
+    if k not in _shape_cache or _shape_cache[k][0] is not arch:
+        _shape_cache[k] = (arch, param_shapes(arch))
+    return _shape_cache[k][1]
 
 
 def synthetic_inputs(n_samples: int, n_ref: int, height: int, width: int, seed: int = 0,

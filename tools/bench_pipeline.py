@@ -13,6 +13,11 @@ a stand-in tokenizer (token ids are irrelevant for timing).  Prints one JSON lin
         as chained pipeline calls with the host round trip of inference.py (PIL image, PNG in memory, reload, ToTensor, upload), timed in
         alternation; one JSON line with both totals, the per-frame times, and the story's split into encode (text encoder + VAE
         encoder), loop, decode, hand-off and scoring from one extra run with a device synchronisation around each part.
+    python tools/bench_pipeline.py --ingest K WxH [--rounds 5]
+        K reference frames of W x H pixels (decoded RGB PIL images, random content) to the pipeline's fp16 [K,3,512,512] on the device:
+        storygen_amd.image.load_reference_images (upload of the raw bytes + sg_image_resize_u8) against the host chain it replaces
+        (PIL resize, ToTensor, cast to fp16, upload), timed in alternation after an untimed pass over both, and the kernel alone on
+        resident bytes (device events); one JSON line.  No network is built.
 dpm = DPM-Solver++(2M), diffusers' DPMSolverMultistepScheduler defaults (storygen_amd.scheduler.DPMSolverMultistepSchedule)."""
 import argparse
 import json
@@ -50,7 +55,10 @@ def main():
     ap.add_argument("--compare", default="", help="comma-separated scheduler:steps[:eta] list, timed in alternation")
     ap.add_argument("--rounds", type=int, default=3, help="timed calls per configuration")
     ap.add_argument("--story", type=int, default=0, metavar="K", help="time a K-frame story against K chained calls with the host round trip")
+    ap.add_argument("--ingest", nargs=2, metavar=("K", "WxH"), help="time the ingest of K raw W x H frames against the host chain")
     args = ap.parse_args()
+    if args.ingest:
+        return ingest(args)
     def parse(c):
         f = c.split(":")
         return f[0], int(f[1]), float(f[2]) if len(f) > 2 else 0.0
@@ -98,6 +106,54 @@ def main():
                           "seconds_max": round(srt[-1], 4), "seconds_all": [round(v, 4) for v in samples],
                           "ms_per_step_incl_everything": round(med / steps * 1e3, 2), "image_shape": list(img.shape),
                           "finite": bool(torch.isfinite(torch.as_tensor(img)).all())}))
+
+
+def ingest(args):
+    import numpy as np
+    from PIL import Image
+    from storygen_amd import ops
+    from storygen_amd.image import load_reference_images
+    K, (W, H) = int(args.ingest[0]), (int(v) for v in args.ingest[1].lower().split("x"))
+    dev, size = torch.device("cuda:0"), (512, 512)
+    rng = np.random.default_rng(0)
+    images = [Image.fromarray(rng.integers(0, 256, (H, W, 3), dtype=np.uint8)) for _ in range(K)]
+
+    def host_chain():      # inference.py:84-89 on decoded images, then the pipeline's cast and upload
+        frames = [torch.from_numpy(np.asarray(im.resize(size)).copy()).permute(2, 0, 1).float().div(255) for im in images]
+        return torch.stack(frames).half().to(dev)
+
+    def device_chain():
+        return load_reference_images(images, size=size, device=dev)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, time.perf_counter() - t0
+    a, b = timed(host_chain)[0], timed(device_chain)[0]          # untimed pass: allocator, coefficient tables
+    res = {"host": [], "device": []}
+    for _ in range(args.rounds):
+        for name, fn in (("host", host_chain), ("device", device_chain)):
+            res[name].append(timed(fn)[1])
+    resident = torch.stack([torch.from_numpy(np.array(im)) for im in images]).to(dev)
+    out_f16 = torch.empty(K, 3, size[1], size[0], dtype=torch.float16, device=dev)
+    ops.image_resize(resident, size, out_u8=False, out_f16=out_f16)
+    kernel = []
+    for _ in range(max(args.rounds, 5)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ops.image_resize(resident, size, out_u8=False, out_f16=out_f16)
+        e1.record()
+        torch.cuda.synchronize()
+        kernel.append(e0.elapsed_time(e1) * 1e-3)
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    print(json.dumps({"workload": f"{K} decoded RGB frames of {W}x{H} -> fp16 [{K},3,512,512] on the device; host = PIL resize + ToTensor + "
+                                  "fp16 + upload, device = upload of the bytes + sg_image_resize_u8 (load_reference_images)",
+                      "frames": K, "source": [W, H], "bits_identical": bool(torch.equal(a.view(torch.int16), b.view(torch.int16))),
+                      "host_chain_seconds_median": round(med(res["host"]), 6), "device_chain_seconds_median": round(med(res["device"]), 6),
+                      "kernel_alone_seconds_median": round(med(kernel), 6), "host_chain_seconds_all": [round(t, 6) for t in res["host"]],
+                      "device_chain_seconds_all": [round(t, 6) for t in res["device"]], "kernel_alone_seconds_all": [round(t, 6) for t in kernel]}))
 
 
 def story(args, unet, vae, clip, dev):
