@@ -357,11 +357,11 @@ typedef struct sg_groupnorm_desc {
      * Up to two sources, because x may be a channel concatenation [h | skip] (model/unet_2d_blocks.py:609,626,716) whose halves
      * were written by different launches: source i covers channels [pstats_c0[i], pstats_c0[i] + pstats_nc[i]) of x with
      * partials over pstats_rows[i] pixels each (pstats_nc = the producer's N).  The sources must cover all C channels.
-     * pstats[0] == NULL: none (the kernel makes its own pass).  Only the wide variant uses them (sg_groupnorm_uses_pstats). */
+     * pstats[0] == NULL: none (the kernel makes its own pass).  Only the wide variant uses them (sg_groupnorm_plan: SG_GN_WIDE). */
     const float* pstats[2];
     int32_t pstats_rows[2], pstats_c0[2], pstats_nc[2];
     /* x as the UNREDUCED output of a split-K convolution (sg_conv3x3_desc.defer_reduce), one-launch variant only
-     * (sg_groupnorm_is_fused): x[b, p, c] = sum over the split_count fp32 slices split_ws[z][b*HW + p][c] (slice order) + split_bias[c]
+     * (sg_groupnorm_plan: SG_GN_ONE_LAUNCH): x[b, p, c] = sum over the split_count fp32 slices split_ws[z][b*HW + p][c] (slice order) + split_bias[c]
      * + split_rowbias[b][c] + split_res[b*HW + p][c] — the additions of the convolution's own second pass, in its order, so the
      * values are bit-identical to reduce-then-normalise.  split_out (optional) receives the reduced tensor (fp32, or fp16 when
      * split_out_f32 = 0; with an fp16 split_out — or none and split_round_f16 = 1 — the normalisation sees the fp16-rounded values,
@@ -375,12 +375,26 @@ typedef struct sg_groupnorm_desc {
 } sg_groupnorm_desc;
 
 int sg_groupnorm_nhwc_f16(const sg_groupnorm_desc* d, sg_stream_t stream);
-/* 1 when a GroupNorm of this shape runs as the one-launch kernel (slab of one (batch, group) in registers), else 0 */
-int sg_groupnorm_is_fused(int32_t HW, int32_t C, int32_t groups);
 size_t sg_groupnorm_workspace_bytes(int32_t B, int32_t groups);
-/* 1 if a GroupNorm of this shape would consume producer statistics (the two-launch "wide" variant), 0 if it runs the
- * single-launch register-resident variant, which reads x once anyway: producers then need not emit any. */
-int sg_groupnorm_uses_pstats(int32_t HW, int32_t C, int32_t groups);
+
+/* The launch sg_groupnorm_nhwc_f16 gives a shape (host-only: no pointers, nothing is launched).  It depends on the shape, on whether x
+ * is fp32, on whether producer statistics are supplied (pstats), on the K slices of a split-K input (split_count, 0 = a plain tensor) and
+ * on the gn_* development options; the launcher obeys the same plan.  A shape the launch refuses is refused here with the same message,
+ * e.g. split_count > 0 on a shape that is not the one-launch variant. */
+typedef enum sg_gn_variant {
+    SG_GN_NARROW     = 0,   /* statistics pass + apply pass on 256 threads: fewer than 8 channels per group (or option gn_wide = 0) */
+    SG_GN_WIDE       = 1,   /* the same two passes on 1024 threads; the only variant that takes producer statistics (then one launch) */
+    SG_GN_ONE_LAUNCH = 2    /* the slab of one (batch, group) in registers; the only variant that sums split-K slices */
+} sg_gn_variant;
+typedef struct sg_gn_plan {
+    int32_t variant;                       /* sg_gn_variant */
+    int32_t threads;                       /* per workgroup: 256 or 1024 */
+    int32_t launches;                      /* 1 or 2 */
+    int32_t chunks, rows_per_chunk;        /* statistics pass (and the wide apply pass): row chunks per sample; 0 for the one-launch variant */
+    int32_t apply_blocks, apply_rows;      /* narrow apply pass: workgroups per sample and rows of each; 0 for the other variants */
+} sg_gn_plan;
+int sg_groupnorm_plan(int32_t B, int32_t HW, int32_t C, int32_t groups, int32_t x_f32, int32_t has_pstats, int32_t split_count,
+                      sg_gn_plan* out);
 
 /* LayerNorm over the last dim of x[M, C] (row stride ldx), eps, affine; optionally a second affine output from
  * the same statistics (norm2 and norm4 both normalise the post-self-attention state, attention.py:268,283).

@@ -117,6 +117,11 @@ class AttnPairPlan(C.Structure):
     _fields_ = [("shared", C.c_int32), ("first", C.c_int32), ("p0", AttnPlan), ("p1", AttnPlan), ("workgroups", C.c_int32)]
 
 
+class GnPlan(C.Structure):
+    _fields_ = [("variant", C.c_int32), ("threads", C.c_int32), ("launches", C.c_int32), ("chunks", C.c_int32),
+                ("rows_per_chunk", C.c_int32), ("apply_blocks", C.c_int32), ("apply_rows", C.c_int32)]
+
+
 class FfDesc(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("ldx", C.c_int64),
@@ -174,8 +179,7 @@ SIGNATURES = {
     "sg_gemm_launch_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(C.c_int32)]),
     "sg_conv3x3_launch_plan": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),
     "sg_gemm_pair_launch_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), C.POINTER(C.c_int32)]),
-    "sg_groupnorm_uses_pstats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
-    "sg_groupnorm_is_fused": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "sg_groupnorm_plan": (C.c_int, [C.c_int32] * 7 + [C.POINTER(GnPlan)]),
     "sg_ff_fused_pack_bytes": (C.c_size_t, [C.c_int32]),
     "sg_ff_geglu_fused_f16": (C.c_int, [C.POINTER(FfDesc), C.c_void_p]),
     "sg_gemm_pair_f16": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), C.c_void_p]),

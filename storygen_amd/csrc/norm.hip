@@ -863,18 +863,51 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const LnParams p) {
     }
 }
 
-// Both passes are pure streaming.  Pass 1 wants enough workgroups to pull HBM (>= 1 per CU) but few partial-sum rows
-// (pass 2 re-reads them all in every workgroup); pass 2 wants ~4 workgroups per CU with >= 32 KB of rows each, so that
-// the fixed prologue (partials, gamma/beta) is amortised.
-void gn_geometry(int B, int HW, int C, bool f32, int* nchunks, int* rows_per_chunk, int* apply_blocks, int* apply_rows) {
+// The forward launch of one shape: which of the three variants it gets and every number its grids are sized by.  The launcher obeys
+// it and sg_groupnorm_plan reports it, so the choice and the geometry are written here and nowhere else.  Development options
+// (sg_debug_set_option): gn_no_fused, gn_fused_max = <slab elements>, gn_wide, gn_fused_nt, gn_chunks.
+int gn_plan(int B, int HW, int C, int groups, bool f32, bool pstats, int splits, sg_gn_plan* pl) {
+    const SgOptions& opt = sg_options();
+    const int cpg = C / groups;
+    const long slab = (long)HW * cpg, fused_max = opt.gn_fused_max >= 0 ? opt.gn_fused_max : GNF_DEFAULT_MAX;
+    *pl = sg_gn_plan{};
+    if (cpg % 4 == 0 && slab <= 256L * 4 * GNF_MAXI && slab <= fused_max && !opt.gn_no_fused) {
+        // gn_fused_kernel: 1024 threads for the slabs they can hold (development option gn_fused_nt = 256: A/B), which a split-K
+        // input needs (gn_fused_kernel<true> has that one instantiation); 256 threads x GNF_MAXI items for the larger ones
+        const bool fits1024 = slab <= 1024L * 4 * 4;
+        SG_REQUIRE(!splits || fits1024, "sg_groupnorm: split_ws serves slabs of up to 16384 values");
+        pl->variant = SG_GN_ONE_LAUNCH; pl->launches = 1;
+        pl->threads = splits || (opt.gn_fused_nt == 1024 && fits1024) ? 1024 : 256;
+        return SG_OK;
+    }
+    SG_REQUIRE(!splits, "sg_groupnorm: split_ws needs the one-launch variant (sg_groupnorm_plan)");
+    if (opt.gn_wide != 0 && cpg >= 8 && C / 8 <= GNW_MAX_VPR) {
+        const int rpp = GNW_NT / (C / 8);
+        // One 1024-thread workgroup fits a CU (99 VGPRs), so the launch is ONE round of at most 256 workgroups: 256 / B chunks per
+        // sample (B = 3: 85 chunks of 49 rows = two full passes of the 25 thread rows at 64^2 x 320, where the round-1..3 cap of 64 chunks
+        // left 64 CUs idle and a third, half-empty pass; 128 chunks at B = 3 — a second round — measured 1.6x slower per launch)
+        int want = 256 / B;
+        if (opt.gn_chunks > 0 && want > opt.gn_chunks) want = opt.gn_chunks;     // development option (A/B): 64 = the round-1..3 cap
+        if (want < 1) want = 1;
+        if (want > GNW_MAX_CHUNKS) want = GNW_MAX_CHUNKS;
+        pl->rows_per_chunk = sg_cdiv(HW, want);
+        if (pl->rows_per_chunk < rpp) pl->rows_per_chunk = rpp;   // at least one full pass of the thread rows
+        pl->chunks = sg_cdiv(HW, pl->rows_per_chunk);
+        pl->variant = SG_GN_WIDE; pl->threads = GNW_NT;
+        pl->launches = pstats ? 1 : 2;      // statistics from the producers' epilogues: no pass of its own over x
+        return SG_OK;
+    }
+    // The narrow pair: both passes are pure streaming.  Pass 1 wants enough workgroups to pull HBM (>= 1 per CU) but few partial-sum
+    // rows (pass 2 re-reads them all in every workgroup); pass 2 wants ~4 workgroups per CU with >= 32 KB of rows each, so that
+    // the fixed prologue (partials, gamma/beta) is amortised.
     const int vpr = C / 8, tw = vpr < 256 ? vpr : 256, rpp = 256 / tw;
     int n = sg_cdiv(HW, rpp * 8);                 // >= 8 passes of rows per workgroup
     const int want1 = sg_cdiv(512, B);
     if (n > want1) n = want1;
     if (n > GN_MAX_CHUNKS) n = GN_MAX_CHUNKS;
     if (n < 1) n = 1;
-    *rows_per_chunk = sg_cdiv(HW, n);
-    *nchunks = sg_cdiv(HW, *rows_per_chunk);
+    pl->rows_per_chunk = sg_cdiv(HW, n);
+    pl->chunks = sg_cdiv(HW, pl->rows_per_chunk);
     const long row_bytes = (long)C * (f32 ? 4 : 2);
     int min_rows = (int)((32768 + row_bytes - 1) / row_bytes);
     if (min_rows < 2 * rpp) min_rows = 2 * rpp;
@@ -882,17 +915,18 @@ void gn_geometry(int B, int HW, int C, bool f32, int* nchunks, int* rows_per_chu
     const int want2 = sg_cdiv(1024, B);
     if (a > want2) a = want2;
     if (a < 1) a = 1;
-    *apply_rows = sg_cdiv(HW, a);
-    *apply_blocks = sg_cdiv(HW, *apply_rows);
+    pl->apply_rows = sg_cdiv(HW, a);
+    pl->apply_blocks = sg_cdiv(HW, pl->apply_rows);
+    pl->variant = SG_GN_NARROW; pl->threads = 256; pl->launches = 2;
+    return SG_OK;
 }
 
-// does a GroupNorm of this shape run as the one-launch kernel?
-bool gn_takes_fused(int HW, int C, int groups) {
-    const SgOptions& opt = sg_options();
-    const long fused_max = opt.gn_fused_max >= 0 ? opt.gn_fused_max : GNF_DEFAULT_MAX;
-    const int cpg = C / groups;
-    const long slab = (long)HW * cpg;
-    return cpg % 4 == 0 && slab <= 256L * 4 * GNF_MAXI && slab <= fused_max && !opt.gn_no_fused;
+// what the launcher and the plan query both require of a shape
+int gn_check_shape(int B, int HW, int C, int groups) {
+    SG_REQUIRE(B > 0 && HW > 0 && C > 0 && groups > 0, "sg_groupnorm: bad shape");
+    SG_REQUIRE(C % 8 == 0 && C % groups == 0 && C <= 2560, "sg_groupnorm: C=%d must be a multiple of 8 and of groups, <= 2560", C);
+    SG_REQUIRE(groups <= GN_MAX_GROUPS, "sg_groupnorm: at most %d groups", GN_MAX_GROUPS);
+    return SG_OK;
 }
 
 }  // namespace
@@ -901,26 +935,18 @@ extern "C" size_t sg_groupnorm_workspace_bytes(int32_t B, int32_t groups) {
     return (size_t)B * GNW_MAX_CHUNKS * (size_t)groups * 2 * sizeof(float);
 }
 
-extern "C" int sg_groupnorm_uses_pstats(int32_t HW, int32_t C, int32_t groups) {
-    if (HW <= 0 || C <= 0 || groups <= 0 || C % groups) return 0;
-    const SgOptions& opt = sg_options();
-    const int cpg = C / groups;
-    if (gn_takes_fused(HW, C, groups)) return 0;      // gn_fused_kernel
-    return (opt.gn_wide != 0 && cpg >= 8 && C / 8 <= GNW_MAX_VPR) ? 1 : 0;
-}
-
-extern "C" int sg_groupnorm_is_fused(int32_t HW, int32_t C, int32_t groups) {
-    if (HW <= 0 || C <= 0 || groups <= 0 || C % groups) return 0;
-    return gn_takes_fused(HW, C, groups) ? 1 : 0;
+extern "C" int sg_groupnorm_plan(int32_t B, int32_t HW, int32_t C, int32_t groups, int32_t x_f32, int32_t has_pstats, int32_t split_count,
+                                 sg_gn_plan* out) {
+    SG_REQUIRE(out != nullptr, "sg_groupnorm_plan: null plan");
+    if (const int rc = gn_check_shape(B, HW, C, groups)) return rc;
+    SG_REQUIRE(split_count >= 0, "sg_groupnorm_plan: split_count must be >= 0");
+    return gn_plan(B, HW, C, groups, x_f32 != 0, has_pstats != 0, split_count, out);
 }
 
 extern "C" int sg_groupnorm_nhwc_f16(const sg_groupnorm_desc* d, sg_stream_t stream) {
     SG_REQUIRE(d != nullptr, "sg_groupnorm: null descriptor");
     SG_REQUIRE((d->x || d->split_ws) && d->y && d->gamma && d->beta && d->workspace, "sg_groupnorm: null pointer");
-    SG_REQUIRE(d->B > 0 && d->HW > 0 && d->C > 0 && d->groups > 0, "sg_groupnorm: bad shape");
-    SG_REQUIRE(d->C % 8 == 0 && d->C % d->groups == 0 && d->C <= 2560,
-               "sg_groupnorm: C=%d must be a multiple of 8 and of groups, <= 2560", d->C);
-    SG_REQUIRE(d->groups <= GN_MAX_GROUPS, "sg_groupnorm: at most %d groups", GN_MAX_GROUPS);
+    if (const int rc = gn_check_shape(d->B, d->HW, d->C, d->groups)) return rc;
     SG_REQUIRE(d->ldy % 8 == 0 && d->ldy >= d->C && (d->split_ws || (d->ldx % 8 == 0 && d->ldx >= d->C)), "sg_groupnorm: bad ldx/ldy");
     SG_REQUIRE((d->split_ws || sg_aligned16(d->x)) && sg_aligned16(d->y) && sg_aligned16(d->gamma) && sg_aligned16(d->beta),
                "sg_groupnorm: 16-byte alignment");
@@ -944,15 +970,7 @@ extern "C" int sg_groupnorm_nhwc_f16(const sg_groupnorm_desc* d, sg_stream_t str
         }
         SG_REQUIRE(covered == d->C, "sg_groupnorm: pstats cover %d of %d channels", covered, d->C);
     }
-    hipStream_t st0 = (hipStream_t)stream;
-    // development options (sg_debug_set_option): gn_no_fused, gn_fused_max = <slab elements>, gn_wide
-    const SgOptions& opt = sg_options();
-    const bool no_fused = opt.gn_no_fused != 0, wide = opt.gn_wide != 0;
-    const long fused_max = opt.gn_fused_max >= 0 ? opt.gn_fused_max : GNF_DEFAULT_MAX;
-    const long slab = (long)p.HW * p.cpg;
-    (void)fused_max; (void)no_fused; (void)slab;
     if (d->split_ws) {
-        SG_REQUIRE(gn_takes_fused(p.HW, p.C, p.G), "sg_groupnorm: split_ws needs the one-launch variant (sg_groupnorm_is_fused)");
         SG_REQUIRE(d->split_count >= 2 && d->split_count <= 64 && sg_aligned16(d->split_ws), "sg_groupnorm: split_count in [2, 64], aligned split_ws");
         SG_REQUIRE(!d->pstats[0], "sg_groupnorm: split_ws excludes pstats");
         SG_REQUIRE(!d->split_bias || sg_aligned16(d->split_bias), "sg_groupnorm: split_bias alignment");
@@ -965,50 +983,37 @@ extern "C" int sg_groupnorm_nhwc_f16(const sg_groupnorm_desc* d, sg_stream_t str
         p.sp_res = d->split_res; p.sp_ldr = d->split_ldr; p.sp_res_f32 = d->split_res_f32 ? 1 : 0;
         p.sp_out = d->split_out; p.sp_ldo = d->split_ldo; p.sp_out_f32 = d->split_out_f32 ? 1 : 0;
         p.sp_round = (d->split_out ? !d->split_out_f32 : d->split_round_f16 != 0) ? 1 : 0;
-        SG_REQUIRE((long)p.HW * p.cpg <= 1024L * 4 * 4, "sg_groupnorm: split_ws serves slabs of up to 16384 values");
-        hipLaunchKernelGGL((gn_fused_kernel<true, 1024, 4>), dim3(p.G, d->B), dim3(1024), 0, st0, p);
-        SG_CHECK_LAUNCH("gn_fused<split>");
-        return SG_OK;
     }
-    if (gn_takes_fused(p.HW, p.C, p.G)) {
-        // development option gn_fused_nt = 1024: the 1024-thread instantiation for slabs it can hold (A/B; default 256 threads)
-        if (opt.gn_fused_nt == 1024 && (long)p.HW * p.cpg <= 1024L * 4 * 4)
-            hipLaunchKernelGGL((gn_fused_kernel<false, 1024, 4>), dim3(p.G, d->B), dim3(1024), 0, st0, p);
+    sg_gn_plan pl;
+    if (const int rc = gn_plan(d->B, d->HW, d->C, d->groups, p.x_f32 != 0, p.ps[0] != nullptr, p.sp_splits, &pl)) return rc;
+    p.nchunks = pl.chunks; p.rows_per_chunk = pl.rows_per_chunk; p.apply_rows = pl.apply_rows;
+    const hipStream_t st = (hipStream_t)stream;
+    const dim3 block(pl.threads);
+    switch (pl.variant) {
+    case SG_GN_ONE_LAUNCH:
+        if (p.sp_ws)
+            hipLaunchKernelGGL((gn_fused_kernel<true, 1024, 4>), dim3(p.G, d->B), block, 0, st, p);
+        else if (pl.threads == 1024)
+            hipLaunchKernelGGL((gn_fused_kernel<false, 1024, 4>), dim3(p.G, d->B), block, 0, st, p);
         else
-            hipLaunchKernelGGL((gn_fused_kernel<false, 256, GNF_MAXI>), dim3(p.G, d->B), dim3(256), 0, st0, p);
-        SG_CHECK_LAUNCH("gn_fused");
-        return SG_OK;
-    }
-    if (wide && p.cpg >= 8 && p.C / 8 <= GNW_MAX_VPR) {
-        const int rpp = GNW_NT / (p.C / 8);
-        // One 1024-thread workgroup fits a CU (99 VGPRs), so the launch is ONE round of at most 256 workgroups: 256 / B chunks per
-        // sample (B = 3: 85 chunks of 49 rows = two full passes of the 25 thread rows at 64^2 x 320, where the round-1..3 cap of 64 chunks
-        // left 64 CUs idle and a third, half-empty pass; 128 chunks at B = 3 — a second round — measured 1.6x slower per launch)
-        int want = 256 / d->B;
-        if (opt.gn_chunks > 0 && want > opt.gn_chunks) want = opt.gn_chunks;     // development option (A/B): 64 = the round-1..3 cap
-        if (want < 1) want = 1;
-        if (want > GNW_MAX_CHUNKS) want = GNW_MAX_CHUNKS;
-        p.rows_per_chunk = sg_cdiv(p.HW, want);
-        if (p.rows_per_chunk < rpp) p.rows_per_chunk = rpp;   // at least one full pass of the thread rows
-        p.nchunks = sg_cdiv(p.HW, p.rows_per_chunk);
-        const dim3 grid(p.nchunks, d->B), block(GNW_NT);
-        if (!p.ps[0]) {            // no statistics from the producers' epilogues: own pass over x
-            hipLaunchKernelGGL(gn_stats_wide_kernel, grid, block, 0, st0, p);
+            hipLaunchKernelGGL((gn_fused_kernel<false, 256, GNF_MAXI>), dim3(p.G, d->B), block, 0, st, p);
+        SG_CHECK_LAUNCH(p.sp_ws ? "gn_fused<split>" : "gn_fused");
+        break;
+    case SG_GN_WIDE:
+        if (pl.launches == 2) {
+            hipLaunchKernelGGL(gn_stats_wide_kernel, dim3(pl.chunks, d->B), block, 0, st, p);
             SG_CHECK_LAUNCH("gn_stats_wide");
         }
-        hipLaunchKernelGGL(gn_apply_wide_kernel, grid, block, 0, st0, p);
+        hipLaunchKernelGGL(gn_apply_wide_kernel, dim3(pl.chunks, d->B), block, 0, st, p);
         SG_CHECK_LAUNCH("gn_apply_wide");
-        return SG_OK;
+        break;
+    default:
+        p.ps[0] = p.ps[1] = nullptr;       // the narrow pair keeps its own statistics pass
+        hipLaunchKernelGGL(gn_stats_kernel, dim3(pl.chunks, d->B), block, 0, st, p);
+        SG_CHECK_LAUNCH("gn_stats");
+        hipLaunchKernelGGL(gn_apply_kernel, dim3(pl.apply_blocks, d->B), block, 0, st, p);
+        SG_CHECK_LAUNCH("gn_apply");
     }
-    p.ps[0] = p.ps[1] = nullptr;       // the narrow pair keeps its own statistics pass
-    int apply_blocks = 1;
-    gn_geometry(d->B, d->HW, d->C, d->x_f32 != 0, &p.nchunks, &p.rows_per_chunk, &apply_blocks, &p.apply_rows);
-    dim3 grid(p.nchunks, d->B), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gn_stats_kernel, grid, block, 0, st, p);
-    SG_CHECK_LAUNCH("gn_stats");
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(apply_blocks, d->B), block, 0, st, p);
-    SG_CHECK_LAUNCH("gn_apply");
     return SG_OK;
 }
 

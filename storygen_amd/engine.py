@@ -27,7 +27,7 @@ attention.py:85-128,236-302) around what the MI355X wants rather than around nn.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -310,13 +310,32 @@ class HarvestPlan:
         return seen == {u: u for u in range(n_samples)}
 
 
+class _GnFeed(NamedTuple):
+    """What a GroupNorm that reads a stream tensor needs to know beyond the tensor itself.  Every producer of a stream tensor returns
+    this for its `out`, every consumer takes it for its `x`.  pstats: statistics the producers' epilogues wrote, one (buffer, rows per
+    partial, channels) entry, or two in channel order for a concat [h | skip].  split: the tensor is still the K slices of a split-K
+    convolution, which the GroupNorm must sum (the dict ops.groupnorm(split=...) takes).  Neither: it makes its own pass over x."""
+    pstats: Optional[list] = None
+    split: Optional[dict] = None
+
+    @staticmethod
+    def concat(h: "_GnFeed", skip: "_GnFeed", channels: int) -> "_GnFeed":
+        """For cat = [h | skip] of `channels` columns: the statistics of both parts, when both have some and they cover the columns."""
+        if h.pstats and skip.pstats and h.pstats[0][2] + skip.pstats[0][2] == channels:
+            return _GnFeed(pstats=h.pstats + skip.pstats)
+        return _NO_FEED
+
+
+_NO_FEED = _GnFeed()
+
+
 class _XfPass:
     """What one pass through a transformer derives from the module switches, the engine and its operands: made once per call (at call
     time: the switches are A/B knobs), read by every stage (UNetEngine._xf_*)."""
 
-    def __init__(self, eng: "UNetEngine", xf: _Xf, x: torch.Tensor, out: Optional[torch.Tensor], lvl: int, consume: bool):
+    def __init__(self, eng: "UNetEngine", xf: _Xf, x: torch.Tensor, x_gn: _GnFeed, out: Optional[torch.Tensor], lvl: int, consume: bool):
         L = self.L = eng.lv[lvl]
-        self.xf, self.x, self.out, self.lvl, self.consume, self.guard = xf, x, out, lvl, consume, eng.ln_guard
+        self.xf, self.x, self.x_gn, self.out, self.lvl, self.consume, self.guard = xf, x, x_gn, out, lvl, consume, eng.ln_guard
         self.B, self.hw, self.M, self.C, self.heads = eng.B, eng.hw[lvl], x.shape[0], xf.spec.channels, xf.spec.heads
         self.scale = xf.spec.dim_head ** -0.5
         self.fold = LN_FOLD and self.C % 64 == 0 and self.C // 64 <= 20
@@ -402,15 +421,12 @@ class UNetEngine:
         # path (sg_attn_fwd_f8_d40); text attention and the D = 80 / 160 levels stay fp16
         self.fp8_attention = bool(fp8_attention)
         # GroupNorm statistics as producer epilogues (north-star; HISTORY.md 5): a conv / GEMM whose output feeds a wide GroupNorm also
-        # writes per-(row tile, channel) sums, and that GroupNorm skips its own statistics pass.  Per producer site: one buffer and
-        # the cached answer of sg_*_stats_tile_rows (0 = this launch cannot emit them -> the consumer makes its own pass).
+        # writes per-(row tile, channel) sums, and that GroupNorm skips its own statistics pass.  Per producer site: what its output
+        # hands to a GroupNorm — its buffer with the cached answer of sg_*_stats_tile_rows, or nothing when that answer is 0 (this
+        # launch cannot emit them -> the consumer makes its own pass).
         self.gn_epilogue_stats = GN_EPILOGUE_STATS
-        self._stats_buf: Dict[str, torch.Tensor] = {}
-        self._stats_rows: Dict[str, int] = {}
+        self._stats_site: Dict[str, _GnFeed] = {}
         self._stats_want: Dict[tuple, bool] = {}
-        self._pstats: Dict[int, tuple] = {}           # data_ptr of a produced tensor -> (buffer, rows per partial, channels)
-        self._splits: Dict[str, int] = {}             # conv site -> planned K slices (sg_conv3x3_planned_splits), asked once
-        self._pending_split: Dict[int, dict] = {}     # data_ptr of a tensor whose split-K reduction its GroupNorm consumer will do
         self.text_cache: Dict[str, torch.Tensor] = {}
         # sticky flags of the LayerNorm fold's two assumptions (ops.LN_GUARD_*; include/storygen_hip.h): every producer / consumer of a
         # folded LayerNorm ORs into this word; check_ln_guard() reads it (one 4-byte D2H copy: call it where the host synchronises anyway)
@@ -588,20 +604,6 @@ class UNetEngine:
         ops.copy_rows(t2d[rows:(1 + copies) * rows].unflatten(0, (copies, rows)), src)
 
     # ---- GroupNorm statistics from producer epilogues
-    def _stats_for(self, site: str, lvl: int, n_out: int, query) -> Optional[torch.Tensor]:
-        """The statistics buffer a producer at `site` (output [B*hw[lvl], n_out]) should write, or None.  `query(buf)` -> rows per
-        partial of exactly that launch (ops.*_stats_rows); asked once per site (the plan depends only on the shapes)."""
-        if not self.gn_epilogue_stats or not self._stats_wanted(lvl, n_out):
-            return None
-        rows = self._stats_rows.get(site)
-        if rows is None:
-            M = self.B * self.hw[lvl]
-            buf = torch.empty((M // 64) * 2 * n_out, dtype=torch.float32, device=self.dev)    # enough for any tile height >= 64
-            rows = self._stats_rows[site] = int(query(buf))
-            if rows:
-                self._stats_buf[site] = buf
-        return self._stats_buf.get(site) if rows else None
-
     def _stats_wanted(self, lvl: int, n_out: int) -> bool:
         """Does any GroupNorm that can read a tensor of n_out channels at this level take producer statistics?  Its own width, or the
         wider channel concats [h | skip] of the up blocks (unet_2d_blocks.py:600-601) — e.g. at 16x16 a 1280-channel GroupNorm is
@@ -613,32 +615,20 @@ class UNetEngine:
             self._stats_want[key] = any(ops.groupnorm_uses_pstats(self.hw[lvl], c, self.groups) for c in widths)
         return self._stats_want[key]
 
-    def _publish(self, out: torch.Tensor, site: str, n_out: int):
-        self._pstats[out.data_ptr()] = (self._stats_buf[site], self._stats_rows[site], n_out)
-
-    def _produce(self, site: str, lvl: int, n_out: int, out: torch.Tensor, launch, rows):
-        """A producer of `out` [B*hw[lvl], n_out] that may emit GroupNorm statistics: launch(statistics buffer or None) runs it, rows(buf)
-        is _stats_for's query for exactly that launch."""
-        st = self._stats_for(site, lvl, n_out, rows)
-        launch(st)
-        if st is not None:
-            self._publish(out, site, n_out)
-        else:
-            self._pstats.pop(out.data_ptr(), None)
-
-    def _pstats_of(self, x: torch.Tensor) -> Optional[list]:
-        """Producer statistics covering x [M, C] (one producer, or two for a channel concat [h | skip]), else None."""
-        C = x.shape[1]
-        a = self._pstats.get(x.data_ptr())
-        if a is None:
-            return None
-        if a[2] == C:
-            return [a]
-        if a[2] < C:
-            b = self._pstats.get(x[:, a[2]:].data_ptr())
-            if b is not None and a[2] + b[2] == C:
-                return [a, b]
-        return None
+    def _produce(self, site: str, lvl: int, n_out: int, launch, rows) -> _GnFeed:
+        """A producer of a stream tensor [B*hw[lvl], n_out] that may emit GroupNorm statistics: launch(statistics buffer or None) runs
+        it, rows(buf) -> rows per partial of exactly that launch (ops.*_stats_rows; 0 = it cannot emit them), asked once per site (the
+        plan depends only on the shapes).  Returns what the tensor hands to the GroupNorm that reads it."""
+        feed = _NO_FEED
+        if self.gn_epilogue_stats and self._stats_wanted(lvl, n_out):
+            feed = self._stats_site.get(site)
+            if feed is None:
+                M = self.B * self.hw[lvl]
+                buf = torch.empty((M // 64) * 2 * n_out, dtype=torch.float32, device=self.dev)    # enough for any tile height >= 64
+                n = int(rows(buf))
+                feed = self._stats_site[site] = _GnFeed(pstats=[(buf, n, n_out)]) if n else _NO_FEED
+        launch(feed.pstats[0][0] if feed.pstats else None)
+        return feed
 
     def _defer_splits(self, site: str, lvl: int, cout: int, query) -> int:
         """K slices (> 1) of the convolution at `site` when it may leave its split-K reduction to the GroupNorm that consumes its
@@ -647,7 +637,7 @@ class UNetEngine:
             return 0
         # asked on every call: the plan is host-only arithmetic, but it depends on process state that can change after the first
         # forward (ops.load_tile_table, sg_debug_set_option) — and the GroupNorm must be told the slice count THIS launch uses
-        n = self._splits[site] = int(query())
+        n = int(query())
         return n if n > 1 else 0
 
     def _attention(self, q, k, vt, out, heads: int, scale: float, nk: Optional[int] = None, short: Optional[tuple] = None):
@@ -664,16 +654,16 @@ class UNetEngine:
         else:
             ops.attention(q, k, vt, out, heads, scale, nk=nk, short=short)
 
-    def _resnet(self, rn: _Resnet, x: torch.Tensor, out: torch.Tensor, lvl: int, defer_out: bool = False):
-        """diffusers ResnetBlock2D.  x fp32 [M,Cin] contiguous; out fp32 [M,Cout], possibly a column
-        slice of a concat buffer.  defer_out: the only reader of `out` before anything else is the GroupNorm of the transformer that
-        follows — a split-K conv2 may leave its reduction to it (SPLITK_IN_GN)."""
+    def _resnet(self, rn: _Resnet, x: torch.Tensor, x_gn: _GnFeed, out: torch.Tensor, lvl: int, defer_out: bool = False) -> _GnFeed:
+        """diffusers ResnetBlock2D.  x fp32 [M,Cin] contiguous, x_gn what its producer handed over; out fp32 [M,Cout],
+        possibly a column slice of a concat buffer.  defer_out: the only reader of `out` before anything else is the GroupNorm of the
+        transformer that follows — a split-K conv2 may leave its reduction to it (SPLITK_IN_GN).  Returns the hand-off of `out`."""
         L, M, r, B, hw = self.lv[lvl], x.shape[0], rn.spec, self.B, self.hw[lvl]
         ws = self.ws_split
         p_in, p_mid = self.padded[(lvl, r.cin)], self.padded[(lvl, r.cout)]
         x16 = L["x16"][: M * r.cin].view(M, r.cin) if rn.wsc is not None else None
         ops.groupnorm(x.unflatten(0, (B, hw)), rn.n1g, rn.n1b, p_in, self.groups, self.eps, True, self.ws_gn,
-                      xcopy=None if x16 is None else x16.unflatten(0, (B, hw)), pstats=self._pstats_of(x))
+                      xcopy=None if x16 is None else x16.unflatten(0, (B, hw)), pstats=x_gn.pstats)
         res, forked = x, False
         if rn.wsc is not None:                     # 1x1 shortcut: independent of conv1 -> norm2, runs beside them
             forked = self._fork()
@@ -689,14 +679,12 @@ class UNetEngine:
         d1 = self._defer_splits(r.prefix + ".conv1", lvl, r.cout, lambda: ops.conv3x3_planned_splits(p_in, rn.w1, self._img(h1, lvl), **kw1))
         if d1:      # conv1 -> norm2: the GroupNorm sums the K slices itself; h1 is never stored (fp16 rounding kept: bit-identical)
             ops.conv3x3(p_in, rn.w1, self._img(h1, lvl), defer_reduce=True, **kw1)
-            self._pstats.pop(h1.data_ptr(), None)
             ops.groupnorm(h1.unflatten(0, (B, hw)), rn.n2g, rn.n2b, p_mid, self.groups, self.eps, True, self.ws_gn,
                           split=dict(ws=ws, splits=d1, rowbias=rb, store=False))
         else:
-            self._produce(r.prefix + ".conv1", lvl, r.cout, h1, lambda s: ops.conv3x3(p_in, rn.w1, self._img(h1, lvl), stats=s, **kw1),
-                          lambda buf: ops.conv3x3_stats_rows(p_in, rn.w1, self._img(h1, lvl), stats=buf, **kw1))
-            ops.groupnorm(h1.unflatten(0, (B, hw)), rn.n2g, rn.n2b, p_mid, self.groups, self.eps, True, self.ws_gn,
-                          pstats=self._pstats_of(h1))
+            h1_gn = self._produce(r.prefix + ".conv1", lvl, r.cout, lambda s: ops.conv3x3(p_in, rn.w1, self._img(h1, lvl), stats=s, **kw1),
+                                  lambda buf: ops.conv3x3_stats_rows(p_in, rn.w1, self._img(h1, lvl), stats=buf, **kw1))
+            ops.groupnorm(h1.unflatten(0, (B, hw)), rn.n2g, rn.n2b, p_mid, self.groups, self.eps, True, self.ws_gn, pstats=h1_gn.pstats)
         if forked:
             self._join()
         kw2 = dict(bias=rn.b2, res1=self._img(res, lvl), workspace=ws, x_padded=True)
@@ -705,11 +693,9 @@ class UNetEngine:
             d2 = self._defer_splits(r.prefix + ".conv2", lvl, r.cout, lambda: ops.conv3x3_planned_splits(p_mid, rn.w2, self._img(out, lvl), **kw2))
         if d2:      # conv2 -> Transformer2DModel.norm: that GroupNorm reduces, and stores `out` (the residual of proj_out)
             ops.conv3x3(p_mid, rn.w2, self._img(out, lvl), defer_reduce=True, **kw2)
-            self._pstats.pop(out.data_ptr(), None)
-            self._pending_split[out.data_ptr()] = dict(ws=ws, splits=d2, bias=rn.b2, res1=res.unflatten(0, (B, hw)), store=True)
-            return
-        self._produce(r.prefix + ".conv2", lvl, r.cout, out, lambda s: ops.conv3x3(p_mid, rn.w2, self._img(out, lvl), stats=s, **kw2),
-                      lambda buf: ops.conv3x3_stats_rows(p_mid, rn.w2, self._img(out, lvl), stats=buf, **kw2))
+            return _GnFeed(split=dict(ws=ws, splits=d2, bias=rn.b2, res1=res.unflatten(0, (B, hw)), store=True))
+        return self._produce(r.prefix + ".conv2", lvl, r.cout, lambda s: ops.conv3x3(p_mid, rn.w2, self._img(out, lvl), stats=s, **kw2),
+                             lambda buf: ops.conv3x3_stats_rows(p_mid, rn.w2, self._img(out, lvl), stats=buf, **kw2))
 
     def _text_kv(self, xf: _Xf, lvl: int, use_cache: bool):
         """K and V^T projections of the text embeddings for attn2 (attention.py:192-199): timestep-invariant, so the
@@ -743,12 +729,12 @@ class UNetEngine:
 
     # ---- Transformer2DModel.forward (attention.py:85-128) + BasicTransformerBlock.forward (:236-302) as stages on one _XfPass: x, out,
     # h0..h3 are the fp32 stream, everything that feeds an MFMA is fp16
-    def _transformer(self, xf: _Xf, x: torch.Tensor, out: Optional[torch.Tensor], lvl: int, text: Optional[torch.Tensor],
-                     harvest: Optional[HarvestPlan], consume: bool, text_cache: bool = False):
-        st = _XfPass(self, xf, x, out, lvl, consume)
+    def _transformer(self, xf: _Xf, x: torch.Tensor, x_gn: _GnFeed, out: Optional[torch.Tensor], lvl: int, text: Optional[torch.Tensor],
+                     harvest: Optional[HarvestPlan], consume: bool, text_cache: bool = False) -> _GnFeed:
+        st = _XfPass(self, xf, x, x_gn, out, lvl, consume)
         self._xf_to_harvest(st, harvest)
         self._xf_queries(st)
-        self._xf_back(st, text_cache)
+        return self._xf_back(st, text_cache)
 
     def _xf_to_harvest(self, st: _XfPass, harvest):
         """Everything up to and including the harvested feature (a harvest_only pass needs nothing behind it)."""
@@ -757,16 +743,16 @@ class UNetEngine:
         self._self_projections(st, st.L["h0"], st.h0r, st.L["qk"], st.L["vt"])
         self._xf_harvest(st, plans, self._xf_self_attention(st, plans))
 
-    def _xf_back(self, st: _XfPass, text_cache: bool, shared: bool = False):
+    def _xf_back(self, st: _XfPass, text_cache: bool, shared: bool = False) -> _GnFeed:
         """From the cross-attentions on: everything that depends on more than the hidden states (cfg_shared_head runs what comes before
-        once for the three CFG samples; shared = their ONE query tensor is still the only one)."""
+        once for the three CFG samples; shared = their ONE query tensor is still the only one).  Returns the hand-off of st.out."""
         h3 = self._xf_cross_consume(st, text_cache, shared) if st.consume else self._xf_cross_text(st, text_cache)
-        self._xf_feed_forward(st, h3)
+        return self._xf_feed_forward(st, h3)
 
     def _xf_entry(self, st: _XfPass):
         L, xf, x = st.L, st.xf, st.x
         ops.groupnorm(x.unflatten(0, (st.B, st.hw)), xf.ng, xf.nb, L["gn"].unflatten(0, (st.B, st.hw)), self.groups, 1e-6, False,
-                      self.ws_gn, pstats=self._pstats_of(x), split=self._pending_split.pop(x.data_ptr(), None))   # :99 (eps 1e-6, :55)
+                      self.ws_gn, pstats=st.x_gn.pstats, split=st.x_gn.split)   # :99 (eps 1e-6, :55)
         ops.gemm(L["gn"], xf.w_in, L["h0"], bias=xf.b_in, workspace=self.ws_split, **st.prod(L["h0"], L["ln"], L["lnst0"]))   # proj_in :101
 
     def _self_projections(self, st: _XfPass, h0: torch.Tensor, h0r: torch.Tensor, qk: torch.Tensor, vt: torch.Tensor):
@@ -897,8 +883,8 @@ class UNetEngine:
         ops.gemm(L["att"], xf.w_o2, h3, bias=xf.b_o2, res1=L["h1"], workspace=self.ws_split, **st.prod3(h3))   # :277,295
         return h3
 
-    def _xf_feed_forward(self, st: _XfPass, h3: torch.Tensor):
-        """Feed-forward :298-300 and proj_out + the block's residual :121-123."""
+    def _xf_feed_forward(self, st: _XfPass, h3: torch.Tensor) -> _GnFeed:
+        """Feed-forward :298-300 and proj_out + the block's residual :121-123.  Returns the hand-off of st.out."""
         xf, L, M, C, gd, ws, x, out = st.xf, st.L, st.M, st.C, st.guard, self.ws_split, st.x, st.out
         h4, w_out = L["h4"], xf.w_out
         if st.ff1 and M <= FF_SPLIT_MAX_TOKENS:      # small launch: two workgroups per 128 tokens, partial sums side by side
@@ -921,19 +907,19 @@ class UNetEngine:
         if not st.ff1 and not st.merge:
             ops.gemm(L["ffi"], xf.w_ff2, L["h4"], bias=xf.b_ff2, res1=h3, workspace=ws)   # fp16: only feeds proj_out
         kwo = dict(bias=xf.b_ffo if st.merge else xf.b_out, res1=x, workspace=ws)
-        self._produce(xf.spec.prefix + ".proj_out", st.lvl, C, out,
-                      lambda s: ops.gemm(h4, w_out, out, stats=None if s is None else (s, st.hw), **kwo),
-                      lambda buf: ops.gemm_stats_rows(h4, w_out, out, stats=(buf, st.hw), **kwo))
+        return self._produce(xf.spec.prefix + ".proj_out", st.lvl, C,
+                             lambda s: ops.gemm(h4, w_out, out, stats=None if s is None else (s, st.hw), **kwo),
+                             lambda buf: ops.gemm_stats_rows(h4, w_out, out, stats=(buf, st.hw), **kwo))
 
-    def _sampler_conv(self, prefix: str, h: torch.Tensor, out: torch.Tensor, lvl: int, out_lvl: int, down: bool):
+    def _sampler_conv(self, prefix: str, h: torch.Tensor, out: torch.Tensor, lvl: int, out_lvl: int, down: bool) -> _GnFeed:
         """Downsample2D (3x3 stride 2) / Upsample2D (nearest 2x + 3x3): the fp32 stream tensor is cast into the
-        zero-bordered fp16 conv input first."""
+        zero-bordered fp16 conv input first.  Returns the hand-off of `out`."""
         w, b = self.samplers[prefix]
         pbuf = self.padded[(lvl, h.shape[1])]
         ops.pad_cast(self._img(h, lvl), pbuf)
         kw = dict(stride=2 if down else 1, upsample2x=not down, bias=b, workspace=self.ws_split, x_padded=True)
-        self._produce(prefix, out_lvl, out.shape[1], out, lambda s: ops.conv3x3(pbuf, w, self._img(out, out_lvl), stats=s, **kw),
-                      lambda buf: ops.conv3x3_stats_rows(pbuf, w, self._img(out, out_lvl), stats=buf, **kw))
+        return self._produce(prefix, out_lvl, out.shape[1], lambda s: ops.conv3x3(pbuf, w, self._img(out, out_lvl), stats=s, **kw),
+                             lambda buf: ops.conv3x3_stats_rows(pbuf, w, self._img(out, out_lvl), stats=buf, **kw))
 
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, harvest_slot: Optional[int] = None, consume: bool = False, harvest: Optional[HarvestPlan] = None,
@@ -970,6 +956,7 @@ class UNetEngine:
         last_xf = [a for blk in self.arch.up for a in blk.attns if a is not None][-1].prefix if harvest_only else None
         tk = dict(text_cache=text_cache)
         arch, text, skips = self.arch, self.text_in, self.skips
+        skip_gn: List[_GnFeed] = [_NO_FEED]      # parallel to skips: what each skip tensor hands to a GroupNorm (conv_in: nothing)
         # --- time embedding :392-398, then all 22 time_emb_proj(silu(emb)) in one GEMV bundle.  emb is only ever consumed through
         # silu (resnet.py time_emb_proj), so the second linear writes silu(emb) once instead of every wave of the bundle redoing it
         if self.time_table is not None and self.time_table_on:       # the loop's timesteps were tabulated at prepare() time: one row lookup instead of the chain
@@ -996,20 +983,21 @@ class UNetEngine:
             saved = self._enter_head(1)
             try:
                 sk0 = skips[0][: self.hw[0]]
-                self._resnet(r0, sk0, self.lv[0]["r"], 0, defer_out=True)
-                st = _XfPass(self, xf0, self.lv[0]["r"], None, 0, True)
+                r_gn = self._resnet(r0, sk0, _NO_FEED, self.lv[0]["r"], 0, defer_out=True)
+                st = _XfPass(self, xf0, self.lv[0]["r"], r_gn, None, 0, True)
                 self._xf_to_harvest(st, None)
                 self._xf_queries(st)
             finally:
                 self._leave_head(saved)
             for t2d in (self.lv[0]["r"], self.lv[0]["h1"]):                # proj_out's residual, the attentions' residual
                 self._spread(t2d, 1, 2)
-            self._xf_back(_XfPass(self, xf0, self.lv[0]["r"], skips[1], 0, True), text_cache, shared=True)
+            h_gn = self._xf_back(_XfPass(self, xf0, self.lv[0]["r"], r_gn, skips[1], 0, True), text_cache, shared=True)
+            skip_gn.append(h_gn)
             h, lvl, si = skips[1], 0, 2
         else:
             # --- conv_in :411
             ops.conv_in(self.x_in, self.w_conv_in, self.b_conv_in, self._img(skips[0], 0))
-            h, lvl, si = skips[0], 0, 1
+            h, h_gn, lvl, si = skips[0], _NO_FEED, 0, 1
         # --- down :417-433 — every layer output is a skip tensor, so it is written straight into its skip buffer
         for bi, blk in enumerate(arch.down):
             for j, r in enumerate(blk.resnets):
@@ -1017,26 +1005,28 @@ class UNetEngine:
                     continue                  # done above
                 xf, out = blk.attns[j], skips[si]
                 if xf is None:
-                    self._resnet(self.resnets[r.prefix], h, out, lvl)
+                    h_gn = self._resnet(self.resnets[r.prefix], h, h_gn, out, lvl)
                 else:
                     rt = self.lv[lvl]["r"]
-                    self._resnet(self.resnets[r.prefix], h, rt, lvl, defer_out=True)
-                    self._transformer(self.xfs[xf.prefix], rt, out, lvl, text, harvest, consume, **tk)
+                    r_gn = self._resnet(self.resnets[r.prefix], h, h_gn, rt, lvl, defer_out=True)
+                    h_gn = self._transformer(self.xfs[xf.prefix], rt, r_gn, out, lvl, text, harvest, consume, **tk)
+                skip_gn.append(h_gn)
                 h, si = out, si + 1
             if blk.sampler_prefix:
                 out = skips[si]
-                self._sampler_conv(blk.sampler_prefix, h, out, lvl, lvl + 1, down=True)
+                h_gn = self._sampler_conv(blk.sampler_prefix, h, out, lvl, lvl + 1, down=True)
+                skip_gn.append(h_gn)
                 h, lvl, si = out, lvl + 1, si + 1
-        assert si == len(skips)
+        assert si == len(skips) == len(skip_gn)
         # --- mid :436-445
         L = self.lv[lvl]
         m0, m1 = arch.mid.resnets
-        self._resnet(self.resnets[m0.prefix], h, L["r"], lvl, defer_out=True)
-        self._transformer(self.xfs[arch.mid.attns[0].prefix], L["r"], L["t_out"], lvl, text, harvest, consume, **tk)
+        r_gn = self._resnet(self.resnets[m0.prefix], h, h_gn, L["r"], lvl, defer_out=True)
+        h_gn = self._transformer(self.xfs[arch.mid.attns[0].prefix], L["r"], r_gn, L["t_out"], lvl, text, harvest, consume, **tk)
         blk0 = arch.up[0]
         k = 0                                                                              # index of the up-path resnet
         cat = self.up_cats[k]
-        self._resnet(self.resnets[m1.prefix], L["t_out"], cat[:, : blk0.resnets[0].cin - blk0.skip_channels[0]], lvl)
+        h_gn = self._resnet(self.resnets[m1.prefix], L["t_out"], h_gn, cat[:, : blk0.resnets[0].cin - blk0.skip_channels[0]], lvl)
         # --- up :448-475 — `cat` = [h | skip]: h was written by the previous layer, the skip by the down path
         for bi, blk in enumerate(arch.up):
             L = self.lv[lvl]
@@ -1044,6 +1034,7 @@ class UNetEngine:
             for j, r in enumerate(blk.resnets):
                 si -= 1
                 assert cat.shape[1] == r.cin and skips[si].data_ptr() == cat[:, r.cin - blk.skip_channels[j]:].data_ptr()
+                cat_gn = _GnFeed.concat(h_gn, skip_gn.pop(), r.cin)
                 if j + 1 < nres:
                     nxt = self.up_cats[k + 1]
                     out = nxt[:, : blk.resnets[j + 1].cin - blk.skip_channels[j + 1]]
@@ -1051,13 +1042,13 @@ class UNetEngine:
                     nxt, out = None, L["t_out"]
                 xf = blk.attns[j]
                 if xf is None:
-                    self._resnet(self.resnets[r.prefix], cat, out, lvl)
+                    h_gn = self._resnet(self.resnets[r.prefix], cat, cat_gn, out, lvl)
                 else:
-                    self._resnet(self.resnets[r.prefix], cat, L["r"], lvl, defer_out=True)
+                    r_gn = self._resnet(self.resnets[r.prefix], cat, cat_gn, L["r"], lvl, defer_out=True)
                     if xf.prefix == last_xf:      # harvest_only: the pass ends with its last feature (before that block's text projections)
-                        self._xf_to_harvest(_XfPass(self, self.xfs[xf.prefix], L["r"], None, lvl, consume), harvest)
+                        self._xf_to_harvest(_XfPass(self, self.xfs[xf.prefix], L["r"], r_gn, None, lvl, consume), harvest)
                         return None
-                    self._transformer(self.xfs[xf.prefix], L["r"], out, lvl, text, harvest, consume, **tk)
+                    h_gn = self._transformer(self.xfs[xf.prefix], L["r"], r_gn, out, lvl, text, harvest, consume, **tk)
                 k += 1
                 if nxt is not None:
                     cat = nxt
@@ -1066,13 +1057,13 @@ class UNetEngine:
                 nblk = arch.up[bi + 1]
                 cat = self.up_cats[k]
                 c_h = nblk.resnets[0].cin - nblk.skip_channels[0]
-                self._sampler_conv(blk.sampler_prefix, h, cat[:, :c_h], lvl, lvl - 1, down=False)
+                h_gn = self._sampler_conv(blk.sampler_prefix, h, cat[:, :c_h], lvl, lvl - 1, down=False)
                 lvl -= 1
         assert si == 0 and lvl == 0
         # --- out :477-480
         L = self.lv[0]
         ops.groupnorm(h.unflatten(0, (self.B, self.hw[0])), *self.gn_out, L["gn"].unflatten(0, (self.B, self.hw[0])),
-                      self.groups, self.eps, True, self.ws_gn, pstats=self._pstats_of(h))
+                      self.groups, self.eps, True, self.ws_gn, pstats=h_gn.pstats)
         ops.conv_out(self._img(L["gn"], 0), self.w_conv_out, self.b_conv_out, self.eps_out)
         return self.eps_out
 

@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, AttnPairPlan, AttnPlan, ConvDesc, FfDesc, GemmDesc, GroupNormDesc, check
+from ._lib import AttnDesc, AttnPairPlan, AttnPlan, ConvDesc, FfDesc, GemmDesc, GnPlan, GroupNormDesc, check
 
 lib = _lib.load()
 
@@ -770,14 +770,27 @@ def groupnorm_workspace_bytes(B: int, groups: int) -> int:
     return lib.sg_groupnorm_workspace_bytes(B, groups)
 
 
+# forward GroupNorm variants of a plan (SG_GN_* of include/storygen_hip.h, in that order)
+GN_VARIANTS = ("narrow", "wide", "one_launch")
+
+
+def groupnorm_plan(HW: int, Cc: int, groups: int, B: int = 1, x_f32: bool = False, pstats: bool = False, splits: int = 0) -> tuple:
+    """The launch a groupnorm() call of this shape gets (sg_groupnorm_plan; no launch): (variant, threads per workgroup, launches, chunks
+    and rows per chunk of the statistics pass, workgroups and rows per workgroup of the narrow apply pass), variant one of GN_VARIANTS.
+    pstats: producer statistics are supplied; splits: K slices of a split=... input (refused unless the variant is "one_launch")."""
+    pl = GnPlan()       # passed as it is (ctypes takes its address): cheaper than C.byref, and the engine asks on every forward
+    check(lib.sg_groupnorm_plan(B, HW, Cc, groups, x_f32, pstats, splits, pl), "sg_groupnorm_plan")
+    return (GN_VARIANTS[pl.variant], pl.threads, pl.launches, pl.chunks, pl.rows_per_chunk, pl.apply_blocks, pl.apply_rows)
+
+
 def groupnorm_uses_pstats(HW: int, Cc: int, groups: int) -> bool:
     """True when a GroupNorm of this shape consumes producer statistics (the two-launch wide variant)."""
-    return bool(lib.sg_groupnorm_uses_pstats(HW, Cc, groups))
+    return groupnorm_plan(HW, Cc, groups)[0] == "wide"
 
 
 def groupnorm_is_fused(HW: int, Cc: int, groups: int) -> bool:
     """True when a GroupNorm of this shape runs as the one-launch kernel (the only variant that takes split=...)."""
-    return bool(lib.sg_groupnorm_is_fused(HW, Cc, groups))
+    return groupnorm_plan(HW, Cc, groups)[0] == "one_launch"
 
 
 def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: torch.Tensor, groups: int, eps: float,

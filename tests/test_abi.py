@@ -36,7 +36,7 @@ def _declared_functions():
 
 def test_header_declares_the_expected_surface():
     fns = _declared_functions()
-    for need in ("sg_gemm_f16", "sg_conv3x3_nhwc_f16", "sg_attn_fwd_f16", "sg_groupnorm_nhwc_f16", "sg_layernorm_f16",
+    for need in ("sg_gemm_f16", "sg_conv3x3_nhwc_f16", "sg_attn_fwd_f16", "sg_groupnorm_nhwc_f16", "sg_groupnorm_plan", "sg_layernorm_f16",
                  "sg_timestep_embed_f32", "sg_cfg_ddim_step_f32", "sg_version", "sg_last_error", "sg_device_arch"):
         assert need in fns, need
     assert len(fns) >= 20
@@ -67,7 +67,7 @@ def test_descriptor_layouts_match_a_c_compiler(tmp_path):
     structs = {"sg_gemm_desc": _lib.GemmDesc, "sg_conv3x3_desc": _lib.ConvDesc, "sg_attn_desc": _lib.AttnDesc,
                "sg_groupnorm_desc": _lib.GroupNormDesc, "sg_groupnorm_bwd_desc": _lib.GroupNormBwdDesc,
                "sg_attn_bwd_desc": _lib.AttnBwdDesc, "sg_adamw_desc": _lib.AdamWDesc,
-               "sg_attn_plan": _lib.AttnPlan, "sg_attn_pair_plan": _lib.AttnPairPlan}
+               "sg_attn_plan": _lib.AttnPlan, "sg_attn_pair_plan": _lib.AttnPairPlan, "sg_gn_plan": _lib.GnPlan}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
     for cname, st in structs.items():
         lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')

@@ -103,7 +103,7 @@ def _gn_params(C, dev):
     return _randn((C,), dev, 2, F16), _randn((C,), dev, 3, F16)
 
 
-# (B, H, W, C), 32 groups; the geometry is gn_geometry's (tw = min(C/8, 256) threads per pixel row, rpp = 256 / tw rows per pass)
+# (B, H, W, C), 32 groups; the geometry is the narrow pair's in gn_plan (tw = min(C/8, 256) threads per pixel row, rpp = 256 / tw rows per pass)
 NARROW = [
     (2, 64, 64, 128),    # cpg 4, slab 16384 (the VAE's outer level): rpp 16, 32 chunks of 128 rows = two trips of the 4-row loop, no remainder
     (3, 25, 40, 64),     # cpg 2: rpp 32, 4 chunks of 250 rows: 4-row loop, then 0 to 3 remainder rows depending on the thread row
@@ -117,6 +117,7 @@ NARROW = [
 def _assert_narrow(HW, C, groups=32):
     from storygen_amd import ops
     assert ops.groupnorm_is_fused(HW, C, groups) == 0 and ops.groupnorm_uses_pstats(HW, C, groups) == 0, "no longer the narrow pair"
+    assert ops.groupnorm_plan(HW, C, groups)[:2] == ("narrow", 256)
 
 
 @pytest.mark.parametrize("flavour", ["f16", "resnet"])
@@ -168,6 +169,7 @@ def test_groupnorm_narrow_pair_behind_gn_wide(gpu, B, HW, C):
     from storygen_amd import ops
     x, g, b, ref, silu, eps = _gn_case(gpu, B, HW, C)
     assert ops.groupnorm_uses_pstats(HW, C, 32) == 1, "default: the wide pair"
+    assert ops.groupnorm_plan(HW, C, 32, B=B)[:2] == ("wide", 1024)
     default = _gn_run(x, g, b, torch.empty_like(x), silu, eps)
     with _options(gn_wide=0):
         _assert_narrow(HW, C)
@@ -186,6 +188,7 @@ def test_groupnorm_wide_pair_behind_gn_no_fused(gpu, B, HW, C):
     fused = _gn_run(x, g, b, torch.empty_like(x), silu, eps)
     with _options(gn_no_fused=1):
         assert ops.groupnorm_is_fused(HW, C, 32) == 0 and ops.groupnorm_uses_pstats(HW, C, 32) == 1
+        assert ops.groupnorm_plan(HW, C, 32, B=B)[:2] == ("wide", 1024)
         out = _gn_run(x, g, b, torch.empty_like(x), silu, eps)
     _check(f"groupnorm gn_no_fused=1 {(B, HW, C)}", out, ref)
     _agree(f"groupnorm gn_no_fused=1 vs one-launch {(B, HW, C)}", out, fused)
@@ -200,8 +203,10 @@ def test_groupnorm_one_launch_256_threads(gpu, B, HW, C):
     x, g, b, ref, silu, eps = _gn_case(gpu, B, HW, C)
     assert ops.groupnorm_is_fused(HW, C, 32) == 1
     nt1024 = _gn_run(x, g, b, torch.empty_like(x), silu, eps)
+    assert ops.groupnorm_plan(HW, C, 32, B=B)[:2] == ("one_launch", 1024)
     with _options(gn_fused_nt=256):
         assert ops.groupnorm_is_fused(HW, C, 32) == 1
+        assert ops.groupnorm_plan(HW, C, 32, B=B)[:2] == ("one_launch", 256)
         out = _gn_run(x, g, b, torch.empty_like(x), silu, eps)
     _check(f"groupnorm gn_fused_nt=256 {(B, HW, C)}", out, ref)
     _agree(f"groupnorm 256 vs 1024 threads {(B, HW, C)}", out, nt1024)
@@ -216,6 +221,7 @@ def test_groupnorm_one_launch_256_threads_large_slabs(gpu, B, HW, C, fused):
     x, g, b, ref, silu, eps = _gn_case(gpu, B, HW, C, silu=not fused)
     with _options(gn_fused_nt=256, gn_fused_max=24576):
         assert ops.groupnorm_is_fused(HW, C, 32) == int(fused)
+        assert ops.groupnorm_plan(HW, C, 32, B=B)[:2] == (("one_launch", 256) if fused else ("wide", 1024))
         out = _gn_run(x, g, b, torch.empty_like(x), silu, eps)
     assert ops.groupnorm_is_fused(HW, C, 32) == 0, "options not restored"
     _check(f"groupnorm gn_fused_max=24576 {(B, HW, C)}", out, ref)
@@ -223,10 +229,13 @@ def test_groupnorm_one_launch_256_threads_large_slabs(gpu, B, HW, C, fused):
 
 def test_groupnorm_wide_pair_gn_chunks(gpu):
     """gn_chunks = 64 (64 chunks of 64 rows) against the default 256 / B = 85 wanted (84 chunks of 49 rows, the last one 29)."""
+    from storygen_amd import ops
     B, HW, C = 3, 4096, 320
     x, g, b, ref, silu, eps = _gn_case(gpu, B, HW, C)
     default = _gn_run(x, g, b, torch.empty_like(x), silu, eps)
+    assert ops.groupnorm_plan(HW, C, 32, B=B)[:5] == ("wide", 1024, 2, 84, 49)
     with _options(gn_chunks=64):
+        assert ops.groupnorm_plan(HW, C, 32, B=B)[:5] == ("wide", 1024, 2, 64, 64)
         out = _gn_run(x, g, b, torch.empty_like(x), silu, eps)
     _check("groupnorm gn_chunks=64", out, ref)
     _check("groupnorm default chunking", default, ref)
