@@ -606,6 +606,8 @@ int sg_gaussian_sample_f32(const float* mean, const float* logvar, const float* 
 /* ------------------------------------------------------------------------------------------------------------
  * Front of the CLIP image tower (CLIP-I / CLIP-T scoring of generated frames with a ViT-B/32-class model).  The tower's
  * GEMMs, LayerNorms, attention and activation are the entry points above; these are the pieces before the first layer.
+ * Two front ends: sg_clip_patchify_f16 / _padk_f16 take FLOAT images and resample them in floating point (not quantised on the way);
+ * sg_clip_patchify_u8, below, takes 8-bit frames and computes exactly what the reference's scripts compute on saved images.
  *
  * sg_clip_resize_geometry: the `clip` package's preprocessing geometry (torchvision Resize(S, BICUBIC) then CenterCrop(S)) for
  *   an H x W image: the shorter side becomes S, the longer int(S * long / short); the crop offset per axis is
@@ -630,6 +632,34 @@ int sg_clip_patchify_padk_f16(const float* x, int32_t B, int32_t H, int32_t W, f
                               const float* std, int32_t S, int32_t ps, int32_t Kpad, sg_half* out, int64_t ldo, sg_stream_t stream);
 int sg_clip_embed_patches_f32(const float* patches, int64_t ldp, const float* cls, const float* pos, float* out, int64_t ldo,
                               int32_t B, int32_t T, int32_t C, sg_stream_t stream);
+
+/* sg_clip_patchify_u8: the same patch rows from 8-BIT frames, computed as the reference's evaluation scripts compute them
+ *   (evaluation/calc_CLIP_image.py, calc_CLIP_text.py, calc_Pickscore.py, inference_COCO_val.py:143-148 score saved PIL images): both the
+ *   `clip` package (Resize(S, BICUBIC) on a PIL image) and transformers' CLIPImageProcessor (resample = 3) call Pillow's Image.resize, which
+ *   is no float bicubic but the two 8-bit fixed-point passes documented at sg_image_resize_u8 above, then crop, ToTensor and Normalize.
+ *   One launch; x uint8 [N, Hin, Win, 3] with batch / row strides bsx / ldx in bytes, as sg_image_resize_u8 takes it.
+ *   Resize and crop: Pillow's resize to Hr x Wr with exactly that arithmetic (hcoef / hbounds, vcoef / vbounds: DEVICE copies of
+ *     sg_image_resample_table's output for (Win, Wr) and (Hin, Hr); a pass whose in == out is skipped, its tables NULL), of which only the
+ *     S x S window at (top, left) is computed.  Hr, Wr, top, left are the caller's: the shortest-edge geometry and the centre-crop rule
+ *     (torchvision rounds (size - S) / 2 half to even, sg_clip_resize_geometry; transformers floors it) are host business.
+ *   Normalise: byte b of channel c becomes fp16(((float)b / 255.0f - mean[c]) / std[c]), every operation rounded to fp32 on its own (no
+ *     fused multiply-add, no reciprocal): ToTensor + Normalize of the `clip` package, and bit for bit what transformers' PIL processor
+ *     returns.  mean and std are HOST arrays of 3 floats.
+ *   Patch rows: out[n * P + (y / ps) * (S / ps) + x / ps, c * ps * ps + (y % ps) * ps + x % ps], P = (S / ps)^2: the layout of
+ *     sg_clip_patchify_padk_f16.  Columns [3 ps^2, Kpad) of every row are zeros; every element of columns [0, Kpad) is written exactly
+ *     once, nothing beyond Kpad and nothing outside the output windows is written.  No alignment is required.
+ *   u8 (optional, NULL to skip): uint8 [N, S, S, 3] (bsu / ldu in bytes), the cropped image as Pillow plus the crop give it.
+ *   The scheme is sg_image_resize_u8's: a workgroup owns SG_IMAGE_TILE_W columns x up to SG_IMAGE_TILE_H rows of the crop window, stages the
+ *   horizontal pass of the input rows its vertical taps read in LDS as uint8 and runs the vertical pass from there; the 768 normalised
+ *   values are a table built per workgroup, and the rows per tile are lowered until the staged rows and that table (1536 bytes) fit
+ *   SG_IMAGE_LDS_BYTES together; the zero columns of a patch row are written by the thread that holds the patch's top-left pixel.  Table bounds are forced inside the input: a wrong table gives wrong pixels, never a read outside x.
+ * SG_EINVAL before any launch: a null x / mean / std / out, sizes outside sg_image_resize_u8's limits, S % ps != 0, Kpad % 8 != 0,
+ * 3 ps^2 > Kpad, Kpad > ldo, a crop window that leaves the resized image, a zero std, strides that make a tensor overlap itself, a table
+ * missing for a pass that runs or given for one that is skipped, outputs that overlap each other or the input. */
+int sg_clip_patchify_u8(const uint8_t* x, int64_t bsx, int64_t ldx, int32_t N, int32_t Hin, int32_t Win, int32_t Hr, int32_t Wr, int32_t top,
+                        int32_t left, const float* mean, const float* std, int32_t S, int32_t ps, int32_t Kpad, sg_half* out, int64_t ldo,
+                        uint8_t* u8, int64_t bsu, int64_t ldu, const int32_t* hcoef, const int32_t* hbounds, const int32_t* vcoef,
+                        const int32_t* vbounds, sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Optimizer step of the training loop: /root/reference/train_StorySalon_stage2.py:186-205 builds torch.optim.AdamW

@@ -7,8 +7,12 @@ projected, L2-normalised features; the scripts print the mean over pairs).
     scorer.clip_i(frames, gt_frames).mean(), scorer.clip_t(frames, tokenizer(prompts, ...).input_ids).mean()
 
 Weights are state dicts in transformers naming (CLIPVisionModelWithProjection / CLIPTextModelWithProjection, or one CLIPModel state
-dict passed for both); the tokenizer is the caller's.  Images go through sg_clip_patchify_f16 — the `clip` package's resize (antialiased
-bicubic on the float image), centre crop and normalisation — and ClipVisionEngine; texts through ClipTextEngine and its projection.
+dict passed for both); the tokenizer is the caller's.  The scripts score saved 8-bit images, and so does this when it is given 8-bit
+frames (a uint8 [N,h,w,3] array or tensor, a list of PIL RGB images or uint8 arrays, sizes may differ): sg_clip_patchify_u8 runs Pillow's
+8-bit bicubic resize bit for bit, the centre crop (`crop`, default "torchvision": CenterCrop of the `clip` package), ToTensor and Normalize —
+the scripts' preprocessing exactly.  Float frames are not quantised on the way: they go through sg_clip_patchify_f16, an antialiased float
+bicubic with the same geometry, which differs from the scripts' by up to about one 8-bit level per pixel.  Then ClipVisionEngine; texts
+through ClipTextEngine and its projection.
 Models outside sg_attn_small_f16 (more than 128 tokens, head dim above 64: ViT-H/14) are refused on the host; PickScore's ViT-H/14 runs in
 storygen_amd/pick_score.py.  There is no CPU path."""
 from __future__ import annotations
@@ -17,7 +21,8 @@ from typing import Dict, Optional
 
 import torch
 
-from .encoders import ClipTextEngine, ClipVisionEngine, check_clip_dims
+from . import ops
+from .encoders import ClipTextEngine, ClipVisionEngine, check_clip_dims, is_uint8_images
 
 SD = Dict[str, torch.Tensor]
 VISION_KEYS = ("hidden_size", "num_attention_heads", "image_size", "patch_size")
@@ -50,8 +55,12 @@ def as_nchw(images) -> torch.Tensor:
 
 class ClipScorer:
     def __init__(self, vision_state_dict: SD, vision_config, text_state_dict: Optional[SD] = None, text_config=None, device="cuda",
-                 in_scale: float = 1.0, in_shift: float = 0.0):
-        """in_scale / in_shift map the caller's pixel values onto [0, 1] (defaults: they already are; (0.5, 0.5) for [-1, 1] tensors)."""
+                 in_scale: float = 1.0, in_shift: float = 0.0, crop: str = "torchvision"):
+        """in_scale / in_shift map the caller's float pixel values onto [0, 1] (defaults: they already are; (0.5, 0.5) for [-1, 1] tensors);
+        crop is the centre-crop rule for 8-bit frames (ops.clip_u8_geometry; calc_CLIP_*.py use the `clip` package: "torchvision")."""
+        if crop not in ops.CLIP_CROPS:
+            raise ValueError(f"ClipScorer: crop must be one of {ops.CLIP_CROPS}, got {crop!r}")
+        self.crop = crop
         vc = _cfg(vision_config, VISION_KEYS, "ClipScorer(vision_config)")
         S, ps = int(vc["image_size"]), int(vc["patch_size"])
         if S <= 0 or ps <= 0 or S % ps:
@@ -77,7 +86,10 @@ class ClipScorer:
                                        eps=float(tc.get("layer_norm_eps", 1e-5)), hidden_act=tc.get("hidden_act", "quick_gelu"))
 
     def image_features(self, images) -> torch.Tensor:
-        """Projected image embeddings, fp32 [N, projection_dim] on the device (not normalised)."""
+        """Projected image embeddings, fp32 [N, projection_dim] on the device (not normalised).  images: float frames ([N,H,W,3] array in
+        [0, 1] or NCHW tensor), or 8-bit frames (module docstring)."""
+        if is_uint8_images(images):
+            return self.vision(images, crop=self.crop)[0]
         return self.vision(as_nchw(images), self.in_scale, self.in_shift)[0]
 
     def text_features(self, input_ids: torch.Tensor) -> torch.Tensor:

@@ -1,10 +1,7 @@
 // Image ingest: Pillow's 8-bit bicubic Image.resize (two fixed-point passes with a rounding to uint8 in between) and ToTensor, in one launch.
-#include "common.h"
-#include <math.h>
+#include "image_resample.h"
 
 namespace {
-
-constexpr int PRECISION_BITS = 22;      // Pillow's: 32 - 8 - 2
 
 struct ResizeArgs {
     const uint8_t* x; long bsx, ldx;                      // uint8 [N,Hin,Win,C]
@@ -13,14 +10,6 @@ struct ResizeArgs {
     const int32_t *hcoef, *hbounds, *vcoef, *vbounds;     // null for a skipped pass
     int Hin, Win, Hout, Wout, hks, vks, th, lds_rows, flip;
 };
-
-struct Taps { int first, n; };
-// (first sample, taps) of one output sample, forced inside the input extent and the table row whatever the table says
-__device__ __forceinline__ Taps taps_of(const int32_t* bounds, int i, int in, int ks) {
-    const int first = min(max(bounds[2 * i], 0), in);
-    return {first, min(max(bounds[2 * i + 1], 0), min(ks, in - first))};
-}
-__device__ __forceinline__ int clip8(int ss) { return min(max(ss >> PRECISION_BITS, 0), 255); }
 
 // A workgroup (4 waves) owns th output rows x SG_IMAGE_TILE_W output columns of one image; a wave takes a row at a time, its lanes the
 // row's tw * C bytes.  Both passes needed: the horizontal pass of the input rows [lo, lo + rows) that the tile's vertical taps read goes
@@ -103,19 +92,6 @@ double bicubic_filter(double x) {
     return 0.0;
 }
 
-struct Axis { double scale, filterscale, support; int ksize; };
-Axis axis_of(int in, int out) {
-    Axis ax;
-    ax.scale = (double)in / out;
-    ax.filterscale = ax.scale < 1.0 ? 1.0 : ax.scale;
-    ax.support = 2.0 * ax.filterscale;
-    ax.ksize = 2 * (int)ceil(ax.support) + 1;
-    return ax;
-}
-bool axis_admitted(int in, int out) {
-    return in > 0 && out > 0 && in <= SG_IMAGE_MAX_SIDE && out <= SG_IMAGE_MAX_SIDE && (int64_t)in <= (int64_t)SG_IMAGE_MAX_RATIO * out;
-}
-
 void fill_table(int in, int out, int32_t* coef, int32_t* bounds) {
     const Axis ax = axis_of(in, out);
     double w[SG_IMAGE_MAX_KSIZE];
@@ -144,27 +120,6 @@ void fill_table(int in, int out, int32_t* coef, int32_t* bounds) {
         bounds[2 * xx + 1] = n;
     }
 }
-
-// Input rows that th consecutive output rows read at most: last tap of the last row - first tap of the first row
-// <= (c + (th - 1) scale + support + 0.5) - (c - support + 0.5 - 1).
-int staged_rows(const Axis& ax, int in, int th) {
-    const int bound = (int)floor((th - 1) * ax.scale + 2.0 * ax.support) + 2;
-    return bound < in ? bound : in;
-}
-int tile_rows(int in, int out, int C) {
-    if (in == out) return SG_IMAGE_TILE_H;
-    const Axis ax = axis_of(in, out);
-    int th = SG_IMAGE_TILE_H;
-    while (th > 1 && (int64_t)staged_rows(ax, in, th) * SG_IMAGE_TILE_W * C > SG_IMAGE_LDS_BYTES) --th;
-    return th;
-}
-
-struct Span { uintptr_t lo, hi; };
-Span span_of(const void* p, int64_t bs, int64_t cs, int64_t ld, int N, int chans, int H, int64_t inner, int esz) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return {lo, lo + (uintptr_t)(((int64_t)(N - 1) * bs + (int64_t)(chans - 1) * cs + (int64_t)(H - 1) * ld + inner) * esz)};
-}
-bool overlap(Span a, Span b) { return a.lo < b.hi && b.lo < a.hi; }
 
 }  // namespace
 

@@ -22,6 +22,7 @@ from __future__ import annotations
 import math
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import ops, repack
@@ -173,6 +174,21 @@ class ClipTextEngine:
         return ops.gemm(pooled.to(self.dev, F16).contiguous(), self.proj, out, workspace=self.ws)
 
 
+def is_uint8_images(images) -> bool:
+    """True for what the scorers and ClipVisionEngine treat as 8-bit frames: a uint8 array or tensor, or a list / tuple whose first entry is a
+    PIL image or a uint8 array / tensor.  Anything else (float tensors and arrays) takes the float path."""
+    if isinstance(images, (list, tuple)):
+        if len(images) == 0:
+            return False
+        first = images[0]
+        if hasattr(first, "mode") and hasattr(first, "size") and not isinstance(first, (np.ndarray, torch.Tensor)):      # a PIL image
+            return True
+        images = first
+    if isinstance(images, np.ndarray):
+        return images.dtype == np.uint8
+    return isinstance(images, torch.Tensor) and images.dtype == torch.uint8
+
+
 class ClipVisionEngine:
     """CLIP image tower with its projection head — transformers CLIPVisionTransformer + visual_projection (ViT-B/32 class: at most 128
     tokens, head dim <= 64), fed by sg_clip_patchify_f16: float images of any size in, (image_embeds, last_hidden_state) out.
@@ -222,13 +238,21 @@ class ClipVisionEngine:
         self.stack = _ClipLayers(sd, self.dev, heads, eps, hidden_act, "ClipVisionEngine")
         self.ws = self.stack.ws
 
-    def __call__(self, images: torch.Tensor, in_scale: float = 1.0, in_shift: float = 0.0, mean=CLIP_IMAGE_MEAN,
-                 std=CLIP_IMAGE_STD) -> Tuple[torch.Tensor, torch.Tensor]:
+    def __call__(self, images, in_scale: float = 1.0, in_shift: float = 0.0, mean=CLIP_IMAGE_MEAN, std=CLIP_IMAGE_STD,
+                 crop: str = "torchvision") -> Tuple[torch.Tensor, torch.Tensor]:
         """images float NCHW [B,3,H,W] of any size, values v with in_scale * v + in_shift in [0, 1] -> (image_embeds fp32 [B, projection_dim],
-        last_hidden_state fp32 [B,T,C]).  Resize, centre crop and normalisation are the `clip` package's preprocessing."""
+        last_hidden_state fp32 [B,T,C]).  Resize, centre crop and normalisation are the `clip` package's preprocessing.
+        8-bit frames (is_uint8_images: a uint8 [B,h,w,3] array or tensor, a list of PIL RGB images or uint8 [h,w,3] arrays / tensors, sizes may
+        differ) are preprocessed as the reference's scripts preprocess saved images instead: Pillow's 8-bit bicubic resize bit for bit, the
+        centre crop of `crop` (ops.clip_u8_geometry), ToTensor + Normalize — sg_clip_patchify_u8, one launch per size.  in_scale / in_shift do
+        not apply to them; `crop` applies to them only."""
+        dev, C, T, K = self.dev, self.C, self.T, 3 * self.ps * self.ps
+        if is_uint8_images(images):
+            a16 = self._patch_rows_u8(images, mean, std, crop)
+            B = a16.shape[0] // (T - 1)
+            return self._encode(a16, B)
         if images.dim() != 4 or images.shape[1] != 3:
             raise ValueError(f"ClipVisionEngine: expected [B,3,H,W], got {tuple(images.shape)}")
-        dev, C, T, K = self.dev, self.C, self.T, 3 * self.ps * self.ps
         B = images.shape[0]
         img = images.detach().to(dev, F32).contiguous()
         a16 = torch.empty(B * (T - 1), self.kpad, dtype=F16, device=dev)
@@ -236,6 +260,44 @@ class ClipVisionEngine:
             ops.clip_patchify(img, a16, self.S, self.ps, mean, std, in_scale, in_shift)
         else:
             ops.clip_patchify(img, a16, self.S, self.ps, mean, std, in_scale, in_shift, kpad=self.kpad)
+        return self._encode(a16, B)
+
+    def _patch_rows_u8(self, images, mean, std, crop: str) -> torch.Tensor:
+        """8-bit frames -> the patch GEMM's fp16 operand [B * (T - 1), kpad]; frames of one size share a launch, as image.py groups them."""
+        from .image import _as_u8
+        if crop not in ops.CLIP_CROPS:
+            raise ValueError(f"ClipVisionEngine: crop must be one of {ops.CLIP_CROPS}, got {crop!r}")
+        if isinstance(images, np.ndarray):
+            images = torch.from_numpy(np.ascontiguousarray(images))
+        groups = {}                                          # (h, w, 3) -> [(index, uint8 [h,w,3])], or the whole [B,h,w,3] tensor
+        if isinstance(images, torch.Tensor):
+            if images.dim() != 4 or images.shape[3] != 3 or 0 in images.shape:
+                raise ValueError(f"ClipVisionEngine: uint8 frames must be [B,h,w,3], got {tuple(images.shape)}")
+            groups[tuple(images.shape[1:])] = images
+        else:
+            if len(images) == 0:
+                raise ValueError("ClipVisionEngine: no frames")
+            for i, im in enumerate(images):
+                t = _as_u8(im, 3, "ClipVisionEngine")
+                if t.shape[2] != 3:
+                    raise ValueError(f"ClipVisionEngine: frames are RGB [h,w,3], got {tuple(t.shape)}")
+                groups.setdefault(tuple(t.shape), []).append((i, t))
+        B, P = len(images), self.T - 1
+        a16 = torch.empty(B * P, self.kpad, dtype=F16, device=self.dev)
+        for (h, w, _), members in groups.items():
+            whole = isinstance(members, torch.Tensor) or len(members) == B
+            batch = members.to(self.dev) if isinstance(members, torch.Tensor) else torch.stack([t.to(self.dev) for _, t in members])
+            if batch.stride(3) != 1 or batch.stride(2) != 3:
+                batch = batch.contiguous()
+            rows = a16 if whole else torch.empty(len(members) * P, self.kpad, dtype=F16, device=self.dev)
+            ops.clip_patchify_u8(batch, rows, self.S, self.ps, mean, std, crop=crop, kpad=self.kpad)
+            if not whole:
+                a16.view(B, P, self.kpad)[torch.tensor([i for i, _ in members], device=self.dev)] = rows.view(len(members), P, self.kpad)
+        return a16
+
+    def _encode(self, a16: torch.Tensor, B: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The tower on the patch rows a16 [B * (T - 1), kpad]."""
+        dev, C, T = self.dev, self.C, self.T
         pe = torch.empty(B * (T - 1), C, dtype=F32, device=dev)
         ops.gemm(a16, self.wp, pe, workspace=self.ws)
         e = torch.empty(B * T, C, dtype=F32, device=dev)

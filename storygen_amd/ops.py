@@ -1104,6 +1104,61 @@ def image_resize(x_u8: torch.Tensor, size, flip: bool = False, out_u8=None, out_
     return out_u8, out_f16
 
 
+CLIP_CROPS = ("torchvision", "floor")
+
+
+def clip_u8_geometry(h: int, w: int, S: int, crop: str = "torchvision") -> tuple:
+    """(resized H, resized W, top, left) of the CLIP preprocessing of an h x w image (host only).  Both rules resize alike: the shorter side
+    becomes S, the longer int(S * long / short).  The centre crop's offset per axis is int(round((size - S) / 2.0)), halves to the even
+    integer, under crop="torchvision" (CenterCrop of the `clip` package: sg_clip_resize_geometry) and (size - S) // 2 under crop="floor"
+    (transformers' CLIPImageProcessor); they differ by one pixel where size - S = 3 (mod 4)."""
+    if crop not in CLIP_CROPS:
+        raise ValueError(f"clip_u8_geometry: crop must be one of {CLIP_CROPS}, got {crop!r}")
+    Hr, Wr, top, left = clip_resize_geometry(h, w, S)
+    return (Hr, Wr, top, left) if crop == "torchvision" else (Hr, Wr, (Hr - S) // 2, (Wr - S) // 2)
+
+
+def clip_patchify_u8(x_u8: torch.Tensor, out: torch.Tensor, S: int, ps: int, mean, std, geometry=None, crop: str = "torchvision",
+                     kpad: Optional[int] = None, out_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x_u8 uint8 [N,h,w,3] (any batch / row stride, contiguous pixels) -> out fp16 [N * (S/ps)^2, >= kpad] (kpad defaults to 3*ps*ps rounded
+    up to 8): every frame resized by Pillow's 8-bit bicubic Image.resize, bit for bit, to geometry[:2] = (Hr, Wr), cropped to the S x S
+    window at geometry[2:] = (top, left), normalised as ToTensor + Normalize(mean, std) and cut into patch rows, columns (c, dy, dx), zero
+    in [3*ps*ps, kpad); columns beyond kpad are left alone (sg_clip_patchify_u8, one launch).  geometry None: clip_u8_geometry(h, w, S,
+    crop).  out_u8: optional uint8 [N,S,S,3] receiving the cropped image.  The coefficient tables are image_resize's, kept per (in, out)."""
+    if x_u8.dtype != torch.uint8 or not x_u8.is_cuda:
+        raise TypeError(f"x_u8: expected a CUDA/HIP uint8 tensor, got {x_u8.dtype} on {x_u8.device}")
+    _f16(out, "out")
+    if x_u8.dim() != 4 or x_u8.shape[3] != 3:
+        raise ValueError(f"clip_patchify_u8: x_u8 must be [N,h,w,3], got {tuple(x_u8.shape)}")
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("clip_patchify_u8: mean and std hold one value per channel")
+    N, h, w, _ = x_u8.shape
+    S, ps = int(S), int(ps)
+    if S <= 0 or ps <= 0 or S % ps:
+        raise ValueError(f"clip_patchify_u8: crop size {S} is not a multiple of patch size {ps}")
+    kpad = (3 * ps * ps + 7) & ~7 if kpad is None else int(kpad)
+    rows = N * (S // ps) ** 2
+    if out.dim() != 2 or out.shape[0] != rows or out.shape[1] < kpad:
+        raise ValueError(f"clip_patchify_u8: out must be [{rows}, >= {kpad}], got {tuple(out.shape)}")
+    if out_u8 is not None:
+        if out_u8.dtype != torch.uint8 or not out_u8.is_cuda:
+            raise TypeError(f"out_u8: expected a CUDA/HIP uint8 tensor, got {out_u8.dtype} on {out_u8.device}")
+        if tuple(out_u8.shape) != (N, S, S, 3):
+            raise ValueError(f"clip_patchify_u8: out_u8 must be {(N, S, S, 3)}, got {tuple(out_u8.shape)}")
+    if any(t is not None and (t.stride(3) != 1 or t.stride(2) != 3) for t in (x_u8, out_u8)):
+        raise ValueError("clip_patchify_u8: [.., w, 3] contiguous pixels on x_u8 and out_u8")
+    Hr, Wr, top, left = (int(v) for v in (clip_u8_geometry(h, w, S, crop) if geometry is None else geometry))
+    if Hr <= 0 or Wr <= 0:
+        raise ValueError(f"clip_patchify_u8: the resized size must be positive, got {(Wr, Hr)}")
+    (hc, hb), (vc, vb) = _image_table(w, Wr, x_u8.device), _image_table(h, Hr, x_u8.device)      # (refuses sizes beyond the limits)
+    m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    su = (out_u8.stride(0), out_u8.stride(1)) if out_u8 is not None else (0, 0)
+    check(lib.sg_clip_patchify_u8(x_u8.data_ptr(), x_u8.stride(0), x_u8.stride(1), N, h, w, Hr, Wr, top, left, m, s, S, ps, kpad,
+                                  out.data_ptr(), _row_stride(out, "out"), _p(out_u8), *su, _p(hc), _p(hb), _p(vc), _p(vb), _stream()),
+          "sg_clip_patchify_u8")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ backward pass (config 4)
 # Validated on MI355X in round 2 (tests/test_backward_gpu.py).  Kernels: csrc/backward.hip, attention_bwd.hip; formulas: oracle/storygen_backward.py.
 def layernorm_bwd(x: torch.Tensor, dy1: torch.Tensor, g1: torch.Tensor, out: torch.Tensor, eps: float = 1e-5,

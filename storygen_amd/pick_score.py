@@ -13,18 +13,21 @@ text_projection.weight, logit_scale); the tokenizer is the caller's.  The image 
 (257 tokens, 16 heads of 80) and the zero-padded patch rows of sg_clip_patchify_padk_f16 (patch size 14: 588 -> 592 columns).  The text
 tower (77 tokens, 16 heads of 64, gelu) is the unchanged ClipTextEngine.
 
-Preprocessing is the one of clip_score.py: shortest-edge antialiased bicubic resize, centre crop and normalisation in one kernel.
-transformers' CLIPImageProcessor for this checkpoint (laion/CLIP-ViT-H-14-laion2B-s32B-b79K) uses the same shortest-edge bicubic resize,
-224 x 224 centre crop, mean and std as the `clip` package.  Float frames are NOT quantised to uint8 on the way (the reference's scripts
-score decoded JPEG / PIL images; this scores the float frames the pipeline returns).  There is no CPU path."""
+Preprocessing.  The reference's scripts score decoded JPEG / PIL images through transformers' CLIPImageProcessor for this checkpoint
+(laion/CLIP-ViT-H-14-laion2B-s32B-b79K): Pillow's 8-bit bicubic shortest-edge resize, a 224 x 224 centre crop at (size - 224) // 2, rescale,
+mean and std of the `clip` package.  8-bit frames (a uint8 [N,h,w,3] array or tensor, a list of PIL RGB images or uint8 arrays, sizes may
+differ) get exactly that in one kernel (sg_clip_patchify_u8, `crop` = "floor"): the pixel_values are the processor's, bit for bit.  Float
+frames are not quantised on the way; they keep the path of clip_score.py (antialiased float bicubic, torchvision's crop offset), which
+differs from the processor's by up to about one 8-bit level per pixel.  There is no CPU path."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
 
 import torch
 
+from . import ops
 from .clip_score import TEXT_KEYS, VISION_KEYS, _cfg, _sub, as_nchw
-from .encoders import ClipTextEngine, ClipVisionEngine, check_clip_dims, check_clip_dims_wide
+from .encoders import ClipTextEngine, ClipVisionEngine, check_clip_dims, check_clip_dims_wide, is_uint8_images
 
 SD = Dict[str, torch.Tensor]
 
@@ -54,8 +57,12 @@ def check_pick_config(vc: dict, tc: dict, who: str = "PickScorer") -> None:
 
 
 class PickScorer:
-    def __init__(self, state_dict: SD, config, device="cuda", in_scale: float = 1.0, in_shift: float = 0.0):
-        """in_scale / in_shift map the caller's pixel values onto [0, 1] (defaults: they already are; (0.5, 0.5) for [-1, 1] tensors)."""
+    def __init__(self, state_dict: SD, config, device="cuda", in_scale: float = 1.0, in_shift: float = 0.0, crop: str = "floor"):
+        """in_scale / in_shift map the caller's float pixel values onto [0, 1] (defaults: they already are; (0.5, 0.5) for [-1, 1] tensors);
+        crop is the centre-crop rule for 8-bit frames (ops.clip_u8_geometry; transformers' processor, which the scripts use: "floor")."""
+        if crop not in ops.CLIP_CROPS:
+            raise ValueError(f"PickScorer: crop must be one of {ops.CLIP_CROPS}, got {crop!r}")
+        self.crop = crop
         vc, tc = split_config(config)
         check_pick_config(vc, tc)
         if "logit_scale" not in state_dict:
@@ -77,7 +84,9 @@ class PickScorer:
 
     def image_features(self, images) -> torch.Tensor:
         """Projected image embeddings, fp32 [N, projection_dim] on the device (not normalised).  images: the pipeline's output_type="np" frames
-        [N, H, W, 3] or a float NCHW tensor."""
+        [N, H, W, 3] or a float NCHW tensor, or 8-bit frames (module docstring)."""
+        if is_uint8_images(images):
+            return self.vision(images, crop=self.crop)[0]
         return self.vision(as_nchw(images), self.in_scale, self.in_shift)[0]
 
     def pixel_features(self, pixel_values: torch.Tensor) -> torch.Tensor:

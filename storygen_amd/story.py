@@ -57,7 +57,7 @@ class StoryGenerator:
     def generate(self, prompts: List[str], *, context_frames: int = 3, stage: str = "auto-regressive", samples_per_frame: int = 1,
                  first_frames=None, first_prompts: Optional[List[str]] = None, num_inference_steps: int = 40,
                  guidance_scale: float = 7.0, image_guidance_scale: float = 3.5, eta: float = 0.0, generator=None, height: int = 512,
-                 width: int = 512, output_type: str = "pil") -> StoryOutput:
+                 width: int = 512, output_type: str = "pil", score_uint8: bool = False) -> StoryOutput:
         """One frame per prompt.  Frame j is one pipeline call conditioned on the last min(j + len(first_frames), context_frames) frames
         of the story so far — the caller's `first_frames` (a float [K,3,H,W] tensor in [0, 1], or raw 8-bit images of any size: a list of
         PIL images / uint8 [h,w,3] arrays or a uint8 [K,h,w,3] tensor, resized as Pillow's `.resize((width, height))` + ToTensor by
@@ -70,7 +70,9 @@ class StoryGenerator:
         samples_per_frame > 1: every frame is one call with num_images_per_prompt = samples_per_frame (`generator`: one per sample, as
         inference.py:97-101 builds them; they keep advancing from frame to frame).  The frame kept is np.argmax of
         scorer.best_of(input_ids, frames)'s probabilities on the uint8 frames (inference_COCO_val.py:143-147; the first of equals) —
-        sample 0 without a scorer.  Only the kept frame becomes context.
+        sample 0 without a scorer.  Only the kept frame becomes context.  score_uint8=True hands the scorer the uint8 frames as they are
+        (a PickScorer then preprocesses them exactly as the script's processor preprocesses the saved images); the default converts them to
+        float [S,3,H,W] = uint8 / 255 first, which the scorer resamples in floating point.
 
         output_type: "pil" (list of PIL images), "uint8" (numpy [F,H,W,3]) or "np" (float32 [F,H,W,3] = uint8 / 255: the SAVED frames,
         unlike the pipeline's "np", which is not quantised).  Returns StoryOutput(frames, chosen, scores): chosen[j] the kept sample of
@@ -116,7 +118,7 @@ class StoryGenerator:
             k, probs = 0, None
             if self.scorer is not None and samples_per_frame > 1:
                 ids = self.tokenizer(prompt, padding=True, truncation=True, max_length=77, return_tensors="pt").input_ids
-                _, probs = self.scorer.best_of(ids, u8.permute(0, 3, 1, 2).float() / 255.0)
+                _, probs = self.scorer.best_of(ids, u8 if score_uint8 else u8.permute(0, 3, 1, 2).float() / 255.0)
                 probs = probs.detach().float().cpu()
                 k = int(np.argmax(probs.numpy()))        # inference_COCO_val.py:147
             chosen.append(k)
