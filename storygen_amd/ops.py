@@ -123,6 +123,11 @@ def _row_stride(t: torch.Tensor, name: str) -> int:
     return t.stride(-2)
 
 
+def _view3(t: torch.Tensor) -> tuple:
+    """(pointer, token stride, batch stride) of a 3-D view, in the order the C ABI takes them."""
+    return t.data_ptr(), t.stride(1), t.stride(0)
+
+
 def device_arch() -> int:
     return lib.sg_device_arch()
 
@@ -622,12 +627,11 @@ def attention_f8(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.
     if v8 + nv8 > scratch.data_ptr() + scratch.numel():
         raise ValueError("attention_f8: scratch too small after alignment")
     st = _stream()
-    check(lib.sg_attn_f8_pack(q.data_ptr(), q.stride(1), q.stride(0), q8, B, heads, Nq, 0, st), "sg_attn_f8_pack(q)")
-    check(lib.sg_attn_f8_pack(k.data_ptr(), k.stride(1), k.stride(0), k8, Bk, heads, Nk, 0, st), "sg_attn_f8_pack(k)")
-    check(lib.sg_attn_f8_pack(vt.data_ptr(), vt.stride(1), vt.stride(0), v8, Bk, heads, Nk, 1, st), "sg_attn_f8_pack(vt)")
+    check(lib.sg_attn_f8_pack(*_view3(q), q8, B, heads, Nq, 0, st), "sg_attn_f8_pack(q)")
+    check(lib.sg_attn_f8_pack(*_view3(k), k8, Bk, heads, Nk, 0, st), "sg_attn_f8_pack(k)")
+    check(lib.sg_attn_f8_pack(*_view3(vt), v8, Bk, heads, Nk, 1, st), "sg_attn_f8_pack(vt)")
     with _timed("attention_f8_d40", 4.0 * B * heads * Nq * Nk * 40, f"B{B} H{heads} Nq{Nq} Nk{Nk}"):
-        check(lib.sg_attn_fwd_f8_d40(q8, k8, v8, out.data_ptr(), out.stride(1), out.stride(0), B, heads, Nq, Nk, Bk, scale, st),
-              "sg_attn_fwd_f8_d40")
+        check(lib.sg_attn_fwd_f8_d40(q8, k8, v8, *_view3(out), B, heads, Nq, Nk, Bk, scale, st), "sg_attn_fwd_f8_d40")
     return out
 
 
@@ -643,44 +647,36 @@ def softmax_rows(scores: torch.Tensor, probs: torch.Tensor, scale: float = 1.0) 
     return probs
 
 
+def _attention_qkv(fn, who: str, q, k, v, out, heads, scale, causal, key_bias):
+    """The body of attention_small / attention_enc: `fn` is the library's entry point, `who` the wrapper's name."""
+    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _f16(t, n)
+        if t.dim() != 3 or t.stride(-1) != 1 or t.shape != q.shape:
+            raise ValueError(f"{who}: {n} must be [B,T,H*D] with a contiguous last dimension")
+    B, T, Cq = q.shape
+    if heads <= 0 or Cq % heads:
+        raise ValueError(f"{who}: {Cq} channels do not split into {heads} heads")
+    if key_bias is not None:
+        _f32(key_bias, "key_bias")
+        if tuple(key_bias.shape) != (B, T) or not key_bias.is_contiguous():
+            raise ValueError(f"{who}: key_bias must be a contiguous [B,T] tensor")
+    check(fn(*_view3(q), *_view3(k), *_view3(v), *_view3(out), _p(key_bias), B, heads, T, Cq // heads, float(scale), int(causal), _stream()),
+          fn.__name__)
+    return out
+
+
 def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int, scale: float, causal: bool,
                     key_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Short-sequence attention (T <= 128, head dim <= 64), q/k/v/out [B,T,H*D] token-/batch-strided fp16 views, V not transposed;
     key_bias = optional fp32 [B,T] additive term (padding mask)."""
-    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        _f16(t, n)
-        if t.dim() != 3 or t.stride(-1) != 1 or t.shape != q.shape:
-            raise ValueError(f"attention_small: {n} must be [B,T,H*D] with a contiguous last dimension")
-    B, T, Cq = q.shape
-    if key_bias is not None:
-        _f32(key_bias, "key_bias")
-        if tuple(key_bias.shape) != (B, T) or not key_bias.is_contiguous():
-            raise ValueError("attention_small: key_bias must be a contiguous [B,T] tensor")
-    check(lib.sg_attn_small_f16(q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), v.data_ptr(), v.stride(1),
-                                v.stride(0), out.data_ptr(), out.stride(1), out.stride(0), _p(key_bias), B, heads, T, Cq // heads,
-                                float(scale), int(causal), _stream()), "sg_attn_small_f16")
-    return out
+    return _attention_qkv(lib.sg_attn_small_f16, "attention_small", q, k, v, out, heads, scale, causal, key_bias)
 
 
 def attention_enc(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int, scale: float, causal: bool,
                   key_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Encoder-class attention on the matrix cores (1 <= T <= 1024, head dim a multiple of 8 up to 128: CLIP ViT-H/14), the contract of
     attention_small: q/k/v/out [B,T,H*D] token-/batch-strided fp16 views, V not transposed; key_bias = optional fp32 [B,T] additive term."""
-    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        _f16(t, n)
-        if t.dim() != 3 or t.stride(-1) != 1 or t.shape != q.shape:
-            raise ValueError(f"attention_enc: {n} must be [B,T,H*D] with a contiguous last dimension")
-    B, T, Cq = q.shape
-    if heads <= 0 or Cq % heads:
-        raise ValueError(f"attention_enc: {Cq} channels do not split into {heads} heads")
-    if key_bias is not None:
-        _f32(key_bias, "key_bias")
-        if tuple(key_bias.shape) != (B, T) or not key_bias.is_contiguous():
-            raise ValueError("attention_enc: key_bias must be a contiguous [B,T] tensor")
-    check(lib.sg_attn_enc_f16(q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), v.data_ptr(), v.stride(1),
-                              v.stride(0), out.data_ptr(), out.stride(1), out.stride(0), _p(key_bias), B, heads, T, Cq // heads,
-                              float(scale), int(causal), _stream()), "sg_attn_enc_f16")
-    return out
+    return _attention_qkv(lib.sg_attn_enc_f16, "attention_enc", q, k, v, out, heads, scale, causal, key_bias)
 
 
 ACT_QUICK_GELU, ACT_GELU = 0, 1

@@ -59,6 +59,14 @@ def test_attention_small(gpu, B, T, H, D, causal, bias):
     assert rel_l2(out.cpu(), want.cpu()) < 1.5e-3
 
 
+def test_attention_small_refuses_heads_that_do_not_divide_the_channels(gpu):
+    from storygen_amd import ops
+    q = torch.zeros(1, 8, 40, dtype=F16, device=gpu)
+    for attn in (ops.attention_small, ops.attention_enc):          # one body: the same rule
+        with pytest.raises(ValueError, match="40 channels do not split into 3 heads"):
+            attn(q, q, q, torch.empty_like(q), 3, 1.0, False)
+
+
 def test_act_embed_and_gaussian_kernels(gpu):
     from storygen_amd import ops
     torch.manual_seed(0)
