@@ -333,7 +333,10 @@ def ff_fused(x: torch.Tensor, wpack: torch.Tensor, b2: torch.Tensor, out: torch.
     """out[M, C] (fp16) = Linear2(a * gelu(g)) + b2 + x with [a | g] = Linear1(LayerNorm(x)) + b1 in ONE launch (sg_ff_geglu_fused_f16):
     x fp32 [M, C] (row-strided view allowed), wpack = repack.ff_fused_pack(...) (uint8), b2 fp16 [C].
     split=True (sg_ff_desc.hidden_split): out is [M, 2C] — two workgroups per 128 tokens, each over half of the hidden units; columns
-    [0, C) + columns [C, 2C) = the result (the consumer contracts [y_a | y_b] with [W | W])."""
+    [0, C) + columns [C, 2C) = the result (the consumer contracts [y_a | y_b] with [W | W]).
+    Range: the kernel holds the hidden activation as fp16(a * 2 gelu(g)) (W2 is packed halved) — finite up to |a gelu(g)| = 32752, inf
+    from 32760 on, half the range of the two-launch path (gemm with EPI_GEGLU, then gemm); beyond it that token's output row is
+    inf / NaN."""
     _f32(x, "x"), _f16(b2, "b2"), _f16(out, "out")
     M, Cc = x.shape
     if tuple(out.shape) != (M, 2 * Cc if split else Cc) or b2.numel() != Cc or wpack.dtype != torch.uint8 or not wpack.is_cuda or not wpack.is_contiguous():

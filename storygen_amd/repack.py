@@ -84,7 +84,8 @@ def ff_fused_pack(w1f: torch.Tensor, d1: torch.Tensor, w2: torch.Tensor) -> torc
                of a chunk delivers d1 (to ~2^-22 relative) into the accumulators;
       W2 part: [C rows = output columns][32 halves = the chunk's hidden units] of W2 / 2 (the kernel evaluates 2 gelu(g); halving is
                exact in fp16 down to the subnormals), chunk j of row n at byte n*64 + ((j ^ ((n >> 2) & 3)) << 4).
-    Returns a uint8 tensor [chunks * (w1_part + w2_part)] on w1f's device."""
+    Returns a uint8 tensor [chunks * (w1_part + w2_part)] on w1f's device.  Raises ValueError when a d1 term is not finite in fp16
+    (|d1| >= 65520): hi would be inf and lo -inf or NaN, and the k-step would poison every token."""
     C = w2.shape[0]
     L = ff_fused_layout(C)
     assert tuple(w1f.shape) == (8 * C, C) and tuple(w2.shape) == (C, 4 * C) and d1.numel() == 8 * C
@@ -110,7 +111,9 @@ def ff_fused_pack(w1f: torch.Tensor, d1: torch.Tensor, w2: torch.Tensor) -> torc
     out[:, : L["w1_img"]] = w1_img.contiguous().view(torch.uint8).view(nch, -1)
     dd = d1.to(device=dev, dtype=torch.float32).contiguous().view(nch, 64)[:, pi]            # image row order
     hi = dd.to(torch.float16)
-    lo = (dd - hi.float()).to(torch.float16)
+    if not bool(torch.isfinite(hi).all()):       # |d1| >= 65520 (or not finite): hi = inf, lo = -inf / NaN would poison every token
+        raise ValueError(f"ff_fused_pack: d1 = W1 beta + b1 must be finite in fp16 (|d1| < 65520), got max |d1| = {float(dd.abs().max()):.6g}")
+    lo =(dd - hi.float()).to(torch.float16)
     dimg = torch.zeros(nch, 64, 16, dtype=torch.float16, device=dev)
     dimg[:, :, 0], dimg[:, :, 1] = hi, lo
     out[:, L["w1_img"]: L["w1_part"]] = dimg.view(torch.uint8).view(nch, -1)
