@@ -625,7 +625,9 @@ class UNetEngine:
             if feed is None:
                 M = self.B * self.hw[lvl]
                 buf = torch.empty((M // 64) * 2 * n_out, dtype=torch.float32, device=self.dev)    # enough for any tile height >= 64
-                n = int(rows(buf))
+                # M < 64 (batch 1 on a 32-token level): no tile of >= 64 rows divides an image — and there is nothing to ask with: an
+                # empty buffer has no address, which the query refuses as "no statistics requested"
+                n = int(rows(buf)) if buf.numel() else 0
                 feed = self._stats_site[site] = _GnFeed(pstats=[(buf, n, n_out)]) if n else _NO_FEED
         launch(feed.pstats[0][0] if feed.pstats else None)
         return feed

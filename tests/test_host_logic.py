@@ -798,3 +798,54 @@ def test_library_is_built_without_packed_fp32_arithmetic():
     from storygen_amd import build
     assert "-fno-slp-vectorize" in build.FLAGS
     assert all("-fslp-vectorize" not in f for flags in build.EXTRA_FLAGS.values() for f in flags)
+
+
+def test_engine_refuses_latents_its_layouts_cannot_hold_before_it_allocates():
+    """UNetEngine takes height and width separately and accepts any pair its layouts can hold; the others are refused by the constructor
+    before it repacks a weight or allocates a buffer (no state dict, no weights and a device this host need not have: a constructor that
+    got any further would fail differently).  48x48: 36 tokens at the deepest attention level, the V^T layout needs a multiple of 8;
+    20x32: the 4-level UNet halves the latent three times.  The admissible non-square shapes run in tests/test_unet_nonsquare_gpu.py."""
+    from storygen_amd.arch import SD15_CONFIG, build_arch
+    from storygen_amd.engine import UNetEngine
+    arch = build_arch(SD15_CONFIG)
+    with pytest.raises(ValueError, match="latent 48x48 leaves 36 tokens at attention block .* needs a multiple of 8"):
+        UNetEngine(arch, None, "cuda:0", 1, 48, 48, 0)
+    for h, w in ((20, 32), (32, 20)):
+        with pytest.raises(ValueError, match=f"latent size {h}x{w} must be divisible by 8"):
+            UNetEngine(arch, None, "cuda:0", 1, h, w, 0)
+
+
+def test_engine_asks_for_no_producer_statistics_where_a_level_has_fewer_than_64_rows(monkeypatch):
+    """UNetEngine._produce sizes the statistics buffer (M // 64) * 2 * n_out floats: with M = B * tokens < 64 (batch 1 at a 32-token
+    level) it is empty, an empty tensor has no address, and sg_*_stats_tile_rows refuses a descriptor without one — the engine raised
+    there (found by tests/test_unet_nonsquare_gpu.py::test_batch_1_harvest_engine_16x32_vs_oracle at the stride-2 convolution into the
+    4x8 level).  On the recording stand-in for ops, with every GroupNorm taking producer statistics: at 8x4 (32 and 8 tokens) batch 1
+    neither asks nor hands a launch a statistics buffer, and every site hands its GroupNorm nothing; batch 2 asks at the 32-token level
+    only (M = 64)."""
+    import recording_ops
+    from storygen_amd import engine as E
+    from storygen_amd.arch import build_arch
+    from storygen_amd.synth import synthetic_state_dict
+    cfg = dict(block_out_channels=(64, 128), down_block_types=("CrossAttnDownBlock2D", "DownBlock2D"), layers_per_block=1,
+               up_block_types=("UpBlock2D", "CrossAttnUpBlock2D"), cross_attention_dim=64, attention_head_dim=2)
+    arch = build_arch(cfg)
+    monkeypatch.setitem(recording_ops.QUERIES, "groupnorm_uses_pstats", lambda HW, Cc, groups: True)
+    monkeypatch.setitem(recording_ops.QUERIES, "groupnorm_is_fused", lambda HW, Cc, groups: False)
+    with recording_ops.installed(E) as rec:
+        wts = E.EngineWeights(arch, synthetic_state_dict(arch, 3), "cpu")
+        for batch in (1, 2):
+            eng = E.UNetEngine(arch, None, "cpu", batch, 8, 4, n_ref=1, seq_len=5, splitk_workspace_mb=1, weights=wts)
+            assert eng.hw == [32, 8]
+            rec.reset()
+            eng.forward(harvest_slot=0)
+            eng.forward(consume=True)
+            asked = [e for e in rec.log if e["op"] in ("conv3x3_stats_rows", "gemm_stats_rows")]
+            fed = [e for e in rec.log if e["op"] in ("conv3x3", "gemm") and e["kw"].get("stats") is not None]
+            stats = [e["kw"]["stats"] for e in asked + fed]
+            sizes = [s["T"][2] for s in stats if isinstance(s, dict)] + [s[0]["T"][2] for s in stats if isinstance(s, list)]
+            assert eng._stats_site and all(n > 0 for shape in sizes for n in shape)
+            if batch == 1:
+                assert not asked and not fed and all(not f.pstats for f in eng._stats_site.values())
+            else:
+                # level 0 only, M = 64: one 64-row partial of 64 channels, or of the 128 the upsampling convolution brings up
+                assert asked and fed and {s[0] for s in sizes} == {2 * 64, 2 * 128}
