@@ -142,23 +142,19 @@ constexpr int EPI_PITCH = 68;                         // floats per staged row
 constexpr int EPI_XTR = 64 * EPI_PITCH;               // float offset of a wave's 1 KB extra area: [0,128) LayerNorm coefficients,
                                                       // [128,256) its 64 columns x 2 planes of GroupNorm statistics (or more LN rows)
 constexpr int EPI_WAVE_BYTES = 64 * EPI_PITCH * 4 + 1024;    // 18432
-constexpr int EPIQ_GROUP_BYTES = 64 * EPI_PITCH * 4 + 4 * 1024;     // epi_finish_q: one 64x64 fp32 image + 1 KB per wave of a 2x2 group
+constexpr int EPIQ_GROUP_BYTES = 64 * EPI_PITCH * 4 + 4 * 1024;     // epi_finish, WT = 1: one 64x64 fp32 image + 1 KB per wave of a 2x2 group
 
 constexpr int LN_MAX_PARTS = 20;      // 64-column blocks per token: C <= 1280
 // Prefetched epilogue operands (native clang vectors, not HIP's float4 class: as members of a struct, or as HIP vector classes,
 // the arrays were demoted to scratch memory): pre[k] = row quad k of the fp32 residual, pbias = bias of the lane's 4 columns.
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-#define EPI_PRE_DECL f32x4 pre_f[16]; u32x2 pre_bias
-#define EPI_PRE_ARGS pre_f, pre_bias
-#define EPI_PRE_PARAMS f32x4 (&pre)[16], u32x2& pbias
 
 // Epilogue traffic is streamed once (outputs written, residuals read) as plain 16- / 8-byte accesses: the non-temporal hint on them was
 // measured and not adopted (GEMM family -0.18 ms, GroupNorm +0.11, step equal: HISTORY.md).
-typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void st_stream(float* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
 __device__ __forceinline__ void st_stream(f16* p, const uint2& v) {
-    const u32x2v w = {v.x, v.y};
-    *reinterpret_cast<u32x2v*>(p) = w;
+    const u32x2 w = {v.x, v.y};
+    *reinterpret_cast<u32x2*>(p) = w;
 }
 __device__ __forceinline__ f32x4 ld_stream(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
@@ -171,23 +167,28 @@ __device__ __forceinline__ bool epi_prefetches(const MmaParams& p) {
     return p.res1 != nullptr && (p.flags & SG_F_RES1_F32) && p.splits == 1 && p.mode == SG_EPI_LINEAR;
 }
 
-// (wrows = rows per wave: 64, or 128 for the 128x64-per-wave tiles, which fetch the bias only)
-__device__ __forceinline__ void epi_prefetch(const MmaParams& p, int m0, int n0, int wm, int wn, int lane, EPI_PRE_PARAMS, int wrows = 64, int npre = 16) {
+// A lane owns NQ row quads (16 of a 64x64-per-wave sub-tile, 4 of a 32x32-per-wave strip); rowq = row of its quad 0, cq = its CLAMPED
+// first column.  The first NPRE quads of the residual are fetched here, the rest is read in the epilogue.
+template <int NQ, int NPRE>
+__device__ __forceinline__ void epi_prefetch(const MmaParams& p, int rowq, int cq, f32x4 (&pre)[NQ], u32x2& pbias) {
+    static_assert(NPRE <= NQ, "prefetched row quads");
     if (p.splits > 1 || p.mode != SG_EPI_LINEAR) return;
-    const int rowq = m0 + wm * wrows + (lane >> 4), cq = min(n0 + wn * 64 + 4 * (lane & 15), p.N - 4);
     if (p.bias) pbias = *reinterpret_cast<const u32x2*>(p.bias + cq);
-    if (!epi_prefetches(p) || wrows != 64) return;      // (128 rows per wave: 128 accumulator registers leave no room for 64 more across the last slab)
+    if (NPRE == 0 || !epi_prefetches(p)) return;
     const float* r = reinterpret_cast<const float*>(p.res1) + cq;
     const int mlast = p.M - 1;
 #pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < npre) pre[k] = ld_stream(r + (long)min(rowq + 4 * k, mlast) * p.ldr1);     // (npre < 16: the rest is read in the epilogue)
+    for (int k = 0; k < NPRE; ++k) pre[k] = ld_stream(r + (long)min(rowq + 4 * k, mlast) * p.ldr1);
 }
 
-// Row quads of the fp32 residual prefetched across the last slab: all 16, or 8 where eight waves share a CU's registers (256 per wave:
-// without packed fp32 arithmetic the 256x128 tile's last slab had spilled three of them)
-template <int NW>
-constexpr int epi_npre() { return NW >= 8 ? 8 : 16; }
+// Row quads of the fp32 residual prefetched across the last slab and row quads per load batch of the epilogue, for NW waves of WTM x 2
+// MFMA tiles: everything at once (16 + 16; 4 + 4 for the 32x32 waves), 8 + 8 where eight waves share a CU's registers (256 per wave:
+// without packed fp32 arithmetic the 256x128 tile's last slab had spilled three of the quads), nothing + 8 for 128 rows per wave (128
+// accumulator registers leave no room for 64 more across the last slab).
+template <int NW, int WTM>
+constexpr int epi_npre() { return WTM == 1 ? 4 : WTM == 4 ? 0 : NW >= 8 ? 8 : 16; }
+template <int NW, int WTM>
+constexpr int epi_kb() { return WTM == 1 ? 4 : (WTM == 4 || NW >= 8) ? 8 : 16; }
 
 // LayerNorm fold (consumer side).  The GEMM ran on the RAW fp16 activations x with W' = gamma (.) W, so
 //   LN(x) W^T + b = rstd (x W'^T - mean c) + d,   c_n = sum_k W'_nk,  d_n = sum_k beta_k W_nk + b_n
@@ -237,19 +238,66 @@ __device__ __forceinline__ void store_out4(const MmaParams& p, int gm, int gn, c
     }
 }
 
+// GroupNorm statistics as an epilogue: per-(row tile, channel) sums of the FINAL fp32 values (bias / temb / residual included, before
+// the fp16 rounding).  A lane holds the sums of its row quads for its 4 columns; the 4 lane rows (l >> 4) are added by two exchanges
+// and the wave parks its 64 columns x 2 planes in the second half of its own 1 KB extra area.  The caller then adds the waves of a
+// column block through LDS in fixed order: deterministic, no atomics.
+__device__ __forceinline__ void epi_park_stats(float* xtr, int lr, int lc, float (&cs)[4], float (&cq2)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        cs[e] += __shfl_xor(cs[e], 16, 64); cq2[e] += __shfl_xor(cq2[e], 16, 64);
+        cs[e] += __shfl_xor(cs[e], 32, 64); cq2[e] += __shfl_xor(cq2[e], 32, 64);
+    }
+    if (lr == 0) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            xtr[128 + (4 * lc + e) * 2 + 0] = cs[e];
+            xtr[128 + (4 * lc + e) * 2 + 1] = cq2[e];
+        }
+    }
+}
+
+// LayerNorm fold, producer side: (sum, M2 about the block mean) of the FINAL fp32 values of token row gm in 64-column block `blk`.  The
+// table holds an even number of blocks per token (ln_token_coeffs).  Every |x| of the block is at most |mean| + sqrt(M2): below the fp16
+// maximum the raw copy did not saturate — otherwise say so.
+__device__ __forceinline__ void ln_out_store(const MmaParams& p, int gm, int blk, float sum, float m2) {
+    const int nblk = ((p.N >> 6) + 1) & ~1;
+    *reinterpret_cast<float2*>(p.ln_out + ((size_t)gm * nblk + blk) * 2) = make_float2(sum, m2);
+    if (p.ln_guard && !(fabsf(sum * (1.f / 64.f)) + sqrtf(m2) < 65504.f)) atomicOr(p.ln_guard, SG_LN_GUARD_RANGE);
+}
+
 // Everything after the last MFMA.  NW waves as a WGM x WGN grid, this wave at (wm, wn); m0 / n0 = the workgroup's tile origin.
 // One workgroup barrier (the LDS ring is dead once every wave has left the last slab), then each wave works alone; a second
 // barrier only when GroupNorm statistics are requested (to add up the WGM wave rows).
 // WTM = 4 (round 6, mma_fat_kernel): a wave owns 128x64 = two 64x64 halves, finished one after the other through the SAME staging region
 // (same-wave LDS traffic is in order); the residual of the second half is read here instead of prefetched, the GroupNorm partial sums of
 // the halves are added in registers before the waves' rows meet in LDS (one partial per 128 WGM rows).
-template <int WGM, int WGN, int WTM = 2>
-__device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x16 (&acc)[WTM][2], EPI_PRE_PARAMS,
+// WT = 1 (mma_lat_kernel, 32x32 per wave).  The waves of a workgroup form 2x2 GROUPS; a group
+// owns one 64x64 block of the tile: its four waves write their accumulators into ONE row-major fp32 image (same pitch as above), and
+// after the barrier wave q of the group finishes rows 16 q .. 16 q + 15 of the block — the row-quad scheme of epi_finish with 4 quads
+// per lane instead of 16 (instruction k: lane l holds columns 4 (l & 15) .. +3 of block row 16 q + 4 k + (l >> 4)), so every global
+// access is still 4 rows x 256 contiguous bytes.  Everything the linear epilogue of epi_finish offers except GEGLU: bias, temb row
+// bias, two residuals, fp32 / fp16 outputs, the LayerNorm fold on both sides, GroupNorm partials (one per tile: 32 WGM rows), split-K
+// partial tiles.  Row sums for the LayerNorm partials come from 16-lane exchanges (a row of the strip lives in 16 lanes).
+// Both forms are ONE function: what differs (where the accumulators land in LDS, where the LayerNorm coefficients come from, how a row is
+// summed for ln_out, which partials meet for the GroupNorm statistics) sits under `if constexpr (WT == 2)`; the split-K store and the linear
+// phases (bias / LayerNorm fold, temb row, residuals, stores) are written once, on NQ row quads per lane.  (As a function of their own
+// — or even as a lambda called in place — those phases made the 8-wave 256x128 tile spill: profiles/r25a_gemm_epilogue_helpers_ab.txt.)
+template <int WGM, int WGN, int WT = 2, int WTM = WT>
+__device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x16 (&acc)[WTM][WT], f32x4 (&pre)[WT == 2 ? 16 : 4], u32x2& pbias,
                                            int m0, int n0, int z, int wave, int wm0, int wn, int lane) {
-    constexpr int BN = 64 * WGN, NW = WGM * WGN, NT = 64 * NW, NH = WTM / 2;
+    constexpr int BN = 32 * WT * WGN, NW = WGM * WGN, NT = 64 * NW, NH = WT == 2 ? WTM / 2 : 1, NQ = WT == 2 ? 16 : 4;
     const int lnm = p.ln_mode;
     const int l31 = lane & 31, hi = lane >> 5, lr = lane >> 4, lc = lane & 15;
-    float* stg = reinterpret_cast<float*>(smem + wave * EPI_WAVE_BYTES);
+    // WT = 1: group (gmq, gq) of 2x2 waves, this wave at (wi, wj) = strip q of the group's 64x64 block
+    constexpr int GQ = WGN / 2;
+    const int gmq = wm0 >> 1, gq = wn >> 1, wi = wm0 & 1, wj = wn & 1, q = wi * 2 + wj;
+    char* grp = smem + (gmq * GQ + gq) * EPIQ_GROUP_BYTES;
+    const int rbase = m0 + gmq * 64 + q * 16, cbase = n0 + gq * 64;               // first row of the strip, first column of the block
+    // stg = the fp32 image (the wave's own, or its group's), xtr = this wave's own 1 KB, r0 = image row of the lane's quad 0
+    float* stg = reinterpret_cast<float*>(WT == 2 ? smem + wave * EPI_WAVE_BYTES : grp);
+    float* xtr = WT == 2 ? stg + EPI_XTR : reinterpret_cast<float*>(grp + 64 * EPI_PITCH * 4 + q * 1024);
+    const int r0 = WT == 2 ? lr : q * 16 + lr;
     // the ring is dead once every wave has issued its last fragment reads (each wave's own reads were waited for by its MFMAs).
     // Raw s_barrier: __syncthreads() would also drain vmcnt, i.e. wait for the prefetched residual before the transpose starts.
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -258,71 +306,90 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
     const bool want_stats = p.stats != nullptr;
 #pragma unroll
     for (int half = 0; half < NH; ++half) {
-    const int wm = wm0 * NH + half;              // this half's 64-row block of the tile
+    const int wm = wm0 * NH + half;              // (WT = 2) this half's 64-row block of the tile
+    int rowq, colq;
+    if constexpr (WT == 2) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4*>(stg + (i * 32 + l31) * EPI_PITCH + j * 32 + 8 * g + 4 * hi) =
-                    make_float4(acc[2 * half + i][j][4 * g], acc[2 * half + i][j][4 * g + 1], acc[2 * half + i][j][4 * g + 2],
-                                acc[2 * half + i][j][4 * g + 3]);
-    // same-wave LDS write -> read: in-order within the wave, the compiler's lgkmcnt wait covers it
-    const int rowq = m0 + wm * 64 + lr, colq = n0 + wn * 64 + 4 * lc;
-    float* xtr = stg + EPI_XTR;
-    if (lnm) {               // lane l: coefficients of token row (mode 1) / token column (mode 2) l of this wave's sub-tile
-        *reinterpret_cast<float2*>(xtr + 2 * lane) =
-            ln_token_coeffs(p, lnm == 1 ? min(m0 + wm * 64 + lane, p.M - 1) : min(n0 + wn * 64 + lane, p.N - 1));
-        if (lnm == 2) {      // ... and c / d of row l
-            const int rr = min(m0 + wm * 64 + lane, p.M - 1);
-            *reinterpret_cast<float2*>(xtr + 128 + 2 * lane) = make_float2(p.ln_c[rr], p.ln_d[rr]);
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4*>(stg + (i * 32 + l31) * EPI_PITCH + j * 32 + 8 * g + 4 * hi) =
+                        make_float4(acc[2 * half + i][j][4 * g], acc[2 * half + i][j][4 * g + 1], acc[2 * half + i][j][4 * g + 2],
+                                    acc[2 * half + i][j][4 * g + 3]);
+        // same-wave LDS write -> read: in-order within the wave, the compiler's lgkmcnt wait covers it
+        rowq = m0 + wm * 64 + lr; colq = n0 + wn * 64 + 4 * lc;
+        if (lnm) {               // lane l: coefficients of token row (mode 1) / token column (mode 2) l of this wave's sub-tile
+            *reinterpret_cast<float2*>(xtr + 2 * lane) =
+                ln_token_coeffs(p, lnm == 1 ? min(m0 + wm * 64 + lane, p.M - 1) : min(n0 + wn * 64 + lane, p.N - 1));
+            if (lnm == 2) {      // ... and c / d of row l
+                const int rr = min(m0 + wm * 64 + lane, p.M - 1);
+                *reinterpret_cast<float2*>(xtr + 128 + 2 * lane) = make_float2(p.ln_c[rr], p.ln_d[rr]);
+            }
         }
-    }
-    if (p.mode == SG_EPI_GEGLU && p.splits == 1) {
-        // interleaved layout (groups of 64 rows of W: 32 value rows then the 32 matching gate rows): the wave's columns 0..31 are
-        // values, 32..63 the gates of the SAME 32 outputs.  Lane l: row 8 k + (l >> 3), values 4 (l & 7) .. +3.
-        const int gr = lane >> 3, gc = (lane & 7) * 4;
-        const int gv = n0 + wn * 64 + gc;                         // interleaved column of the 4 values; gates at gv + 32
-        if (gv >= p.N) continue;
-        float bv[4] = {0, 0, 0, 0}, bg[4] = {0, 0, 0, 0};
-        if (p.bias) {
-            H4 a, b;
-            a.u = *reinterpret_cast<const uint2*>(p.bias + gv); b.u = *reinterpret_cast<const uint2*>(p.bias + gv + 32);
+        if (p.mode == SG_EPI_GEGLU && p.splits == 1) {
+            // interleaved layout (groups of 64 rows of W: 32 value rows then the 32 matching gate rows): the wave's columns 0..31 are
+            // values, 32..63 the gates of the SAME 32 outputs.  Lane l: row 8 k + (l >> 3), values 4 (l & 7) .. +3.
+            const int gr = lane >> 3, gc = (lane & 7) * 4;
+            const int gv = n0 + wn * 64 + gc;                         // interleaved column of the 4 values; gates at gv + 32
+            if (gv >= p.N) continue;
+            float bv[4] = {0, 0, 0, 0}, bg[4] = {0, 0, 0, 0};
+            if (p.bias) {
+                H4 a, b;
+                a.u = *reinterpret_cast<const uint2*>(p.bias + gv); b.u = *reinterpret_cast<const uint2*>(p.bias + gv + 32);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { bv[e] = (float)a.h[e]; bg[e] = (float)b.h[e]; }
-        }
-        const int go = (gv >> 6) * 32 + (gv & 31);                // interleaved column -> output column
-        float cv[4] = {0, 0, 0, 0}, cg[4] = {0, 0, 0, 0};
-        if (lnm == 1) {      // folded LayerNorm: value / gate = rstd (acc - mean c) + d  (d carries the bias)
-            const f32x4 a = *reinterpret_cast<const f32x4*>(p.ln_c + gv), b = *reinterpret_cast<const f32x4*>(p.ln_c + gv + 32);
-            const f32x4 c = *reinterpret_cast<const f32x4*>(p.ln_d + gv), d = *reinterpret_cast<const f32x4*>(p.ln_d + gv + 32);
-            cv[0] = a.x; cv[1] = a.y; cv[2] = a.z; cv[3] = a.w; cg[0] = b.x; cg[1] = b.y; cg[2] = b.z; cg[3] = b.w;
-            bv[0] += c.x; bv[1] += c.y; bv[2] += c.z; bv[3] += c.w; bg[0] += d.x; bg[1] += d.y; bg[2] += d.z; bg[3] += d.w;
-        }
+                for (int e = 0; e < 4; ++e) { bv[e] = (float)a.h[e]; bg[e] = (float)b.h[e]; }
+            }
+            const int go = (gv >> 6) * 32 + (gv & 31);                // interleaved column -> output column
+            float cv[4] = {0, 0, 0, 0}, cg[4] = {0, 0, 0, 0};
+            if (lnm == 1) {      // folded LayerNorm: value / gate = rstd (acc - mean c) + d  (d carries the bias)
+                const f32x4 a = *reinterpret_cast<const f32x4*>(p.ln_c + gv), b = *reinterpret_cast<const f32x4*>(p.ln_c + gv + 32);
+                const f32x4 c = *reinterpret_cast<const f32x4*>(p.ln_d + gv), d = *reinterpret_cast<const f32x4*>(p.ln_d + gv + 32);
+                cv[0] = a.x; cv[1] = a.y; cv[2] = a.z; cv[3] = a.w; cg[0] = b.x; cg[1] = b.y; cg[2] = b.z; cg[3] = b.w;
+                bv[0] += c.x; bv[1] += c.y; bv[2] += c.z; bv[3] += c.w; bg[0] += d.x; bg[1] += d.y; bg[2] += d.z; bg[3] += d.w;
+            }
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int row = 8 * k + gr, gm = m0 + wm * 64 + row;
-            const float4 a = *reinterpret_cast<const float4*>(stg + row * EPI_PITCH + gc);
-            const float4 b = *reinterpret_cast<const float4*>(stg + row * EPI_PITCH + 32 + gc);
-            float2 mr = make_float2(0.f, 1.f);
-            if (lnm == 1) mr = *reinterpret_cast<const float2*>(xtr + 2 * row);
-            if (gm >= p.M) continue;
-            const float va[4] = {a.x, a.y, a.z, a.w}, ga[4] = {b.x, b.y, b.z, b.w};
-            float o[4];
+            for (int k = 0; k < 8; ++k) {
+                const int row = 8 * k + gr, gm = m0 + wm * 64 + row;
+                const float4 a = *reinterpret_cast<const float4*>(stg + row * EPI_PITCH + gc);
+                const float4 b = *reinterpret_cast<const float4*>(stg + row * EPI_PITCH + 32 + gc);
+                float2 mr = make_float2(0.f, 1.f);
+                if (lnm == 1) mr = *reinterpret_cast<const float2*>(xtr + 2 * row);
+                if (gm >= p.M) continue;
+                const float va[4] = {a.x, a.y, a.z, a.w}, ga[4] = {b.x, b.y, b.z, b.w};
+                float o[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-                o[e] = (fmaf(mr.y, va[e], bv[e]) - mr.x * cv[e]) * gelu_erf_f(fmaf(mr.y, ga[e], bg[e]) - mr.x * cg[e]);
-            store_out4(p, gm, go, o);
+                for (int e = 0; e < 4; ++e)
+                    o[e] = (fmaf(mr.y, va[e], bv[e]) - mr.x * cv[e]) * gelu_erf_f(fmaf(mr.y, ga[e], bg[e]) - mr.x * cg[e]);
+                store_out4(p, gm, go, o);
+            }
+            continue;
         }
-        continue;
+    } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<float4*>(stg + (wi * 32 + l31) * EPI_PITCH + wj * 32 + 8 * g + 4 * hi) =
+                make_float4(acc[0][0][4 * g], acc[0][0][4 * g + 1], acc[0][0][4 * g + 2], acc[0][0][4 * g + 3]);
+        // LayerNorm coefficients depend on no other wave: computed while the other waves are still writing the image
+        if (lnm == 1) {          // rows are tokens: lane l -> strip row l & 15 (the four lane rows compute the same value; one stores)
+            const float2 c = ln_token_coeffs(p, min(rbase + lc, p.M - 1));
+            if (lr == 0) *reinterpret_cast<float2*>(xtr + 2 * lc) = c;
+        } else if (lnm == 2) {   // columns are tokens: lane l -> block column l; c / d of the strip's rows
+            *reinterpret_cast<float2*>(xtr + 2 * lane) = ln_token_coeffs(p, min(cbase + lane, p.N - 1));
+            const int rr = min(rbase + lc, p.M - 1);
+            if (lr == 0) *reinterpret_cast<float2*>(xtr + 128 + 2 * lc) = make_float2(p.ln_c[rr], p.ln_d[rr]);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        rowq = rbase + lr; colq = cbase + 4 * lc;
     }
     const bool col_ok = colq < p.N;
-    if (p.splits > 1) {   // raw fp32 partial tile; the epilogue happens in splitk_reduce_kernel
+    if (p.splits > 1) {   // raw fp32 partial tile; the epilogue happens in splitk_reduce_kernel (or in the consumer)
         float* wsz = p.ws + (size_t)z * p.M * p.N + colq;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int row = 4 * k + lr, gm = rowq + 4 * k;
+        for (int k = 0; k < NQ; ++k) {
+            const int row = 4 * k + r0, gm = rowq + 4 * k;
             const float4 v = *reinterpret_cast<const float4*>(stg + row * EPI_PITCH + 4 * lc);
             if (gm < p.M && col_ok) st_stream(wsz + (size_t)gm * p.N, f32x4{v.x, v.y, v.z, v.w});
         }
@@ -335,7 +402,7 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
     // (a2 + h) + (a3 + h): the same tensor as both residuals is read once
     const bool res2_same = p.res2 != nullptr && p.res2 == p.res1 && p.ldr2 == p.ldr1 && r1f32 == r2f32;
     const int cq = min(colq, p.N - 4), mlast = p.M - 1;
-    float v[16][4];
+    float v[NQ][4];
     {
         float bias4[4] = {0, 0, 0, 0};
         if (p.bias) {
@@ -348,8 +415,8 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
             const float c4[4] = {lc4.x, lc4.y, lc4.z, lc4.w};
             const float d4[4] = {ld4.x + bias4[0], ld4.y + bias4[1], ld4.z + bias4[2], ld4.w + bias4[3]};
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const float4 a = *reinterpret_cast<const float4*>(stg + (4 * k + lr) * EPI_PITCH + 4 * lc);
+            for (int k = 0; k < NQ; ++k) {
+                const float4 a = *reinterpret_cast<const float4*>(stg + (4 * k + r0) * EPI_PITCH + 4 * lc);
                 const float2 mr = *reinterpret_cast<const float2*>(xtr + 2 * (4 * k + lr));
                 const float av[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
@@ -360,8 +427,8 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const float2 t = *reinterpret_cast<const float2*>(xtr + 2 * (4 * lc + e)); mrx[e] = t.x; mry[e] = t.y; }
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const float4 a = *reinterpret_cast<const float4*>(stg + (4 * k + lr) * EPI_PITCH + 4 * lc);
+            for (int k = 0; k < NQ; ++k) {
+                const float4 a = *reinterpret_cast<const float4*>(stg + (4 * k + r0) * EPI_PITCH + 4 * lc);
                 const float2 cd = *reinterpret_cast<const float2*>(xtr + 128 + 2 * (4 * k + lr));
                 const float av[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
@@ -369,17 +436,17 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const float4 a = *reinterpret_cast<const float4*>(stg + (4 * k + lr) * EPI_PITCH + 4 * lc);
+            for (int k = 0; k < NQ; ++k) {
+                const float4 a = *reinterpret_cast<const float4*>(stg + (4 * k + r0) * EPI_PITCH + 4 * lc);
                 v[k][0] = a.x + bias4[0]; v[k][1] = a.y + bias4[1]; v[k][2] = a.z + bias4[2]; v[k][3] = a.w + bias4[3];
             }
         }
     }
     // (loads of a term in batches of KB row quads: all 16 at once, or 8 + 8 where the register budget is 256 per wave)
-    constexpr int KB = (NH > 1 || NW >= 8) ? 8 : 16;      // (eight waves per workgroup: 256 registers per wave)
+    constexpr int KB = epi_kb<NW, WTM>();
     auto add_f32 = [&](const float* base, long ld) __attribute__((always_inline)) {
 #pragma unroll
-        for (int kb = 0; kb < 16; kb += KB) {
+        for (int kb = 0; kb < NQ; kb += KB) {
             float4 t[KB];
 #pragma unroll
             for (int k = 0; k < KB; ++k) t[k] = *reinterpret_cast<const float4*>(base + (long)min(rowq + 4 * (kb + k), mlast) * ld + cq);
@@ -388,11 +455,11 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
         }
     };
     auto add_f16 = [&](const f16* base, long ld) __attribute__((always_inline)) {
-        uint2 t[16];
+        uint2 t[NQ];
 #pragma unroll
-        for (int k = 0; k < 16; ++k) t[k] = *reinterpret_cast<const uint2*>(base + (long)min(rowq + 4 * k, mlast) * ld + cq);
+        for (int k = 0; k < NQ; ++k) t[k] = *reinterpret_cast<const uint2*>(base + (long)min(rowq + 4 * k, mlast) * ld + cq);
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
+        for (int k = 0; k < NQ; ++k) {
             H4 h; h.u = t[k];
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[k][e] += (float)h.h[e];
@@ -400,7 +467,7 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
     };
     if (p.rowbias) {
 #pragma unroll
-        for (int kb = 0; kb < 16; kb += KB) {
+        for (int kb = 0; kb < NQ; kb += KB) {
             float4 t[KB];
 #pragma unroll
             for (int k = 0; k < KB; ++k)
@@ -415,7 +482,7 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
             if constexpr (NH > 1) {                       // 128 rows per wave: nothing was prefetched (registers); two batches of 8 row quads
                 const float* r = reinterpret_cast<const float*>(p.res1) + cq;
 #pragma unroll
-                for (int kb = 0; kb < 16; kb += 8) {
+                for (int kb = 0; kb < NQ; kb += 8) {
                     f32x4 t[8];
 #pragma unroll
                     for (int k = 0; k < 8; ++k) t[k] = ld_stream(r + (long)min(rowq + 4 * (kb + k), mlast) * p.ldr1);
@@ -426,13 +493,13 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
                     }
                 }
             } else {
-                if constexpr (epi_npre<NW>() < 16) {
+                if constexpr (epi_npre<NW, WTM>() < NQ) {
                     const float* r = reinterpret_cast<const float*>(p.res1) + cq;
 #pragma unroll
-                    for (int k = epi_npre<NW>(); k < 16; ++k) pre[k] = ld_stream(r + (long)min(rowq + 4 * k, mlast) * p.ldr1);
+                    for (int k = epi_npre<NW, WTM>(); k < NQ; ++k) pre[k] = ld_stream(r + (long)min(rowq + 4 * k, mlast) * p.ldr1);
                 }
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
+                for (int k = 0; k < NQ; ++k) {
                     v[k][0] = fmaf(w, pre[k].x, v[k][0]); v[k][1] = fmaf(w, pre[k].y, v[k][1]);
                     v[k][2] = fmaf(w, pre[k].z, v[k][2]); v[k][3] = fmaf(w, pre[k].w, v[k][3]);
                 }
@@ -447,7 +514,7 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
         else add_f16(reinterpret_cast<const f16*>(p.res2), p.ldr2);
     }
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {
+    for (int k = 0; k < NQ; ++k) {
         const int gm = rowq + 4 * k;
         if (gm < p.M && col_ok) {
             store_out4(p, gm, colq, v[k]);
@@ -456,307 +523,101 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
         }
     }
     if (p.ln_out) {
-        // LayerNorm fold, producer side: per token (row) and per 64-column block (this wave's columns) the sum and the M2 about the
-        // block mean of the FINAL fp32 values.  The wave puts them back into its staging image and lane l reads row l whole
-        // (16 x 16 B, conflict-free at this pitch): 64 adds + 64 fmas per lane, no cross-lane traffic, fixed order.
+        if constexpr (WT == 2) {
+            // LayerNorm fold, producer side: per token (row) and per 64-column block (this wave's columns) the sum and the M2 about the
+            // block mean of the FINAL fp32 values.  The wave puts them back into its staging image and lane l reads row l whole
+            // (16 x 16 B, conflict-free at this pitch): 64 adds + 64 fmas per lane, no cross-lane traffic, fixed order.
 #pragma unroll
-        for (int k = 0; k < 16; ++k)
-            *reinterpret_cast<float4*>(stg + (4 * k + lr) * EPI_PITCH + 4 * lc) = make_float4(v[k][0], v[k][1], v[k][2], v[k][3]);
-        float sum = 0.f, m2 = 0.f, mean = 0.f;
-        if constexpr (NH > 1) {      // 128 rows per wave: the row is read twice, eight quads at a time (registers)
+            for (int k = 0; k < 16; ++k)
+                *reinterpret_cast<float4*>(stg + (4 * k + lr) * EPI_PITCH + 4 * lc) = make_float4(v[k][0], v[k][1], v[k][2], v[k][3]);
+            float sum = 0.f, m2 = 0.f, mean = 0.f;
+            if constexpr (NH > 1) {      // 128 rows per wave: the row is read twice, eight quads at a time (registers)
 #pragma unroll
-            for (int pass = 0; pass < 2; ++pass) {
+                for (int pass = 0; pass < 2; ++pass) {
 #pragma unroll
-                for (int qb = 0; qb < 16; qb += 8) {
-                    float4 rv[8];
+                    for (int qb = 0; qb < 16; qb += 8) {
+                        float4 rv[8];
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) rv[q] = *reinterpret_cast<const float4*>(stg + lane * EPI_PITCH + 4 * (qb + q));
+                        for (int q = 0; q < 8; ++q) rv[q] = *reinterpret_cast<const float4*>(stg + lane * EPI_PITCH + 4 * (qb + q));
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        if (pass == 0) {
-                            sum += (rv[q].x + rv[q].y) + (rv[q].z + rv[q].w);
-                        } else {
-                            const float a = rv[q].x - mean, b = rv[q].y - mean, c = rv[q].z - mean, d = rv[q].w - mean;
-                            m2 = fmaf(a, a, m2); m2 = fmaf(b, b, m2); m2 = fmaf(c, c, m2); m2 = fmaf(d, d, m2);
+                        for (int q = 0; q < 8; ++q) {
+                            if (pass == 0) {
+                                sum += (rv[q].x + rv[q].y) + (rv[q].z + rv[q].w);
+                            } else {
+                                const float a = rv[q].x - mean, b = rv[q].y - mean, c = rv[q].z - mean, d = rv[q].w - mean;
+                                m2 = fmaf(a, a, m2); m2 = fmaf(b, b, m2); m2 = fmaf(c, c, m2); m2 = fmaf(d, d, m2);
+                            }
                         }
                     }
+                    if (pass == 0) mean = sum * (1.f / 64.f);
                 }
-                if (pass == 0) mean = sum * (1.f / 64.f);
+            } else {
+                float4 rv[16];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) rv[q] = *reinterpret_cast<const float4*>(stg + lane * EPI_PITCH + 4 * q);
+#pragma unroll
+                for (int q = 0; q < 16; ++q) sum += (rv[q].x + rv[q].y) + (rv[q].z + rv[q].w);
+                mean = sum * (1.f / 64.f);
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const float a = rv[q].x - mean, b = rv[q].y - mean, c = rv[q].z - mean, d = rv[q].w - mean;
+                    m2 = fmaf(a, a, m2); m2 = fmaf(b, b, m2); m2 = fmaf(c, c, m2); m2 = fmaf(d, d, m2);
+                }
+            }
+            const int gm = m0 + wm * 64 + lane;
+            if (gm < p.M && n0 + wn * 64 < p.N) {
+                ln_out_store(p, gm, (n0 >> 6) + wn, sum, m2);
             }
         } else {
-            float4 rv[16];
+            // LayerNorm fold, producer side: (sum, M2 about the block mean) of the FINAL fp32 values per token and 64-column block.  A row of
+            // the strip lives in the 16 lanes that share lane >> 4: four exchanges per quantity, fixed order.
+            float s4[4], m4[4];
 #pragma unroll
-            for (int q = 0; q < 16; ++q) rv[q] = *reinterpret_cast<const float4*>(stg + lane * EPI_PITCH + 4 * q);
+            for (int k = 0; k < 4; ++k) s4[k] = (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
 #pragma unroll
-            for (int q = 0; q < 16; ++q) sum += (rv[q].x + rv[q].y) + (rv[q].z + rv[q].w);
-            mean = sum * (1.f / 64.f);
+            for (int o = 1; o < 16; o <<= 1)
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const float a = rv[q].x - mean, b = rv[q].y - mean, c = rv[q].z - mean, d = rv[q].w - mean;
-                m2 = fmaf(a, a, m2); m2 = fmaf(b, b, m2); m2 = fmaf(c, c, m2); m2 = fmaf(d, d, m2);
+                for (int k = 0; k < 4; ++k) s4[k] += __shfl_xor(s4[k], o, 64);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float mean = s4[k] * (1.f / 64.f);
+                const float a = v[k][0] - mean, b = v[k][1] - mean, c = v[k][2] - mean, d = v[k][3] - mean;
+                m4[k] = fmaf(a, a, fmaf(b, b, fmaf(c, c, d * d)));
             }
-        }
-        const int gm = m0 + wm * 64 + lane;
-        if (gm < p.M && n0 + wn * 64 < p.N) {
-            *reinterpret_cast<float2*>(p.ln_out + ((size_t)gm * (((p.N >> 6) + 1) & ~1) + ((n0 >> 6) + wn)) * 2) = make_float2(sum, m2);
-            // every |x| of the block is at most |mean| + sqrt(M2): below the fp16 maximum the raw copy did not saturate
-            if (p.ln_guard && !(fabsf(mean) + sqrtf(m2) < 65504.f)) atomicOr(p.ln_guard, SG_LN_GUARD_RANGE);
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) m4[k] += __shfl_xor(m4[k], o, 64);
+            if (lc == 0 && cbase < p.N) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (rowq + 4 * k < p.M) ln_out_store(p, rowq + 4 * k, (n0 >> 6) + gq, s4[k], m4[k]);
+            }
         }
     }
     }       // halves
-    if (want_stats && p.mode == SG_EPI_LINEAR && p.splits == 1) {
-        float* xtr = stg + EPI_XTR;
-        // GroupNorm statistics as an epilogue: per-(row tile, channel) sums of the FINAL fp32 values (bias / temb / residual
-        // included, before the fp16 rounding).  A lane holds 16 rows of its 4 columns; the 4 lane groups (l >> 4) are added by two
-        // exchanges, the WGM wave rows through LDS in fixed order: deterministic, no atomics.
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            cs[e] += __shfl_xor(cs[e], 16, 64); cq2[e] += __shfl_xor(cq2[e], 16, 64);
-            cs[e] += __shfl_xor(cs[e], 32, 64); cq2[e] += __shfl_xor(cq2[e], 32, 64);
-        }
-        // every wave parks its 64 columns x 2 planes in the second half of its own extra area
-        if (lr == 0) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                xtr[128 + (4 * lc + e) * 2 + 0] = cs[e];
-                xtr[128 + (4 * lc + e) * 2 + 1] = cq2[e];
-            }
-        }
+    if (want_stats && (WT == 1 || p.mode == SG_EPI_LINEAR) && p.splits == 1) {
+        // (the partials of a column block meet through LDS in fixed order: the WGM wave rows, or — WT = 1 — the 4 strips of each of the
+        // WGM / 2 groups)
+        epi_park_stats(xtr, lr, lc, cs, cq2);
         __syncthreads();
         for (int idx = threadIdx.x; idx < BN * 2; idx += NT) {
             const int plane = idx / BN, col = idx - plane * BN;
             const int gn = n0 + col;
             if (gn < p.N) {
                 float s = 0.f;
+                if constexpr (WT == 2) {
 #pragma unroll
-                for (int w = 0; w < WGM; ++w)
-                    s += reinterpret_cast<const float*>(smem + (w * WGN + (col >> 6)) * EPI_WAVE_BYTES)[EPI_XTR + 128 + (col & 63) * 2 + plane];
-                p.stats[((size_t)(m0 / (32 * WTM * WGM)) * 2 + plane) * p.N + gn] = s;
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Epilogue of the 32x32-per-wave kernel (mma_lat_kernel, WT = 1 in mma_pipe_body).  The waves of a workgroup form 2x2 GROUPS; a group
-// owns one 64x64 block of the tile: its four waves write their accumulators into ONE row-major fp32 image (same pitch as above), and
-// after the barrier wave q of the group finishes rows 16 q .. 16 q + 15 of the block — the row-quad scheme of epi_finish with 4 quads
-// per lane instead of 16 (instruction k: lane l holds columns 4 (l & 15) .. +3 of block row 16 q + 4 k + (l >> 4)), so every global
-// access is still 4 rows x 256 contiguous bytes.  Everything the linear epilogue of epi_finish offers except GEGLU: bias, temb row
-// bias, two residuals, fp32 / fp16 outputs, the LayerNorm fold on both sides, GroupNorm partials (one per tile: 32 WGM rows), split-K
-// partial tiles.  Row sums for the LayerNorm partials come from 16-lane exchanges (a row of the strip lives in 16 lanes).
-template <int WGN>
-__device__ __forceinline__ void epi_prefetch_q(const MmaParams& p, int m0, int n0, int wave, int lane, f32x4 (&pre)[4], u32x2& pbias) {
-    if (p.splits > 1 || p.mode != SG_EPI_LINEAR) return;
-    const int wm32 = wave / WGN, wn32 = wave % WGN, q = (wm32 & 1) * 2 + (wn32 & 1);
-    const int rowq = m0 + (wm32 >> 1) * 64 + q * 16 + (lane >> 4), cq = min(n0 + (wn32 >> 1) * 64 + 4 * (lane & 15), p.N - 4);
-    if (p.bias) pbias = *reinterpret_cast<const u32x2*>(p.bias + cq);
-    if (!epi_prefetches(p)) return;
-    const float* r = reinterpret_cast<const float*>(p.res1) + cq;
-    const int mlast = p.M - 1;
+                    for (int w = 0; w < WGM; ++w)
+                        s += reinterpret_cast<const float*>(smem + (w * WGN + (col >> 6)) * EPI_WAVE_BYTES)[EPI_XTR + 128 + (col & 63) * 2 + plane];
+                } else {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) pre[k] = ld_stream(r + (long)min(rowq + 4 * k, mlast) * p.ldr1);
-}
-
-template <int WGM, int WGN>
-__device__ __forceinline__ void epi_finish_q(const MmaParams& p, char* smem, f32x16& acc, f32x4 (&pre)[4], u32x2& pbias,
-                                             int m0, int n0, int z, int wave, int lane) {
-    constexpr int GN_ = WGN / 2, NW = WGM * WGN, BM = 32 * WGM, BN = 32 * WGN, NT = 64 * NW;
-    const int wm32 = wave / WGN, wn32 = wave % WGN;
-    const int gm_ = wm32 >> 1, gn_ = wn32 >> 1, wi = wm32 & 1, wj = wn32 & 1, q = wi * 2 + wj;
-    const int l31 = lane & 31, hi = lane >> 5, lr = lane >> 4, lc = lane & 15;
-    const int lnm = p.ln_mode;
-    char* grp = smem + (gm_ * GN_ + gn_) * EPIQ_GROUP_BYTES;
-    float* stg = reinterpret_cast<float*>(grp);
-    float* xtr = reinterpret_cast<float*>(grp + 64 * EPI_PITCH * 4 + q * 1024);     // this wave's own 1 KB
-    const int rbase = m0 + gm_ * 64 + q * 16, cbase = n0 + gn_ * 64;                 // first row of the strip, first column of the block
-    // the ring is dead once every wave has issued its last fragment reads (raw barrier: a prefetched residual stays in flight)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+                    for (int g = 0; g < WGM / 2; ++g)
 #pragma unroll
-    for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<float4*>(stg + (wi * 32 + l31) * EPI_PITCH + wj * 32 + 8 * g + 4 * hi) =
-            make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
-    // LayerNorm coefficients depend on no other wave: computed while the other waves are still writing the image
-    if (lnm == 1) {          // rows are tokens: lane l -> strip row l & 15 (the four lane rows compute the same value; one stores)
-        const float2 c = ln_token_coeffs(p, min(rbase + lc, p.M - 1));
-        if (lr == 0) *reinterpret_cast<float2*>(xtr + 2 * lc) = c;
-    } else if (lnm == 2) {   // columns are tokens: lane l -> block column l; c / d of the strip's rows
-        *reinterpret_cast<float2*>(xtr + 2 * lane) = ln_token_coeffs(p, min(cbase + lane, p.N - 1));
-        const int rr = min(rbase + lc, p.M - 1);
-        if (lr == 0) *reinterpret_cast<float2*>(xtr + 128 + 2 * lc) = make_float2(p.ln_c[rr], p.ln_d[rr]);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const int rowq = rbase + lr, colq = cbase + 4 * lc;
-    const bool col_ok = colq < p.N;
-    const float* img = stg + (q * 16 + lr) * EPI_PITCH + 4 * lc;             // + 4 k rows
-    if (p.splits > 1) {      // raw fp32 partial tile; the epilogue happens in splitk_reduce_kernel (or in the consumer)
-        float* wsz = p.ws + (size_t)z * p.M * p.N + colq;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int gm = rowq + 4 * k;
-            const float4 v = *reinterpret_cast<const float4*>(img + 4 * k * EPI_PITCH);
-            if (gm < p.M && col_ok) st_stream(wsz + (size_t)gm * p.N, f32x4{v.x, v.y, v.z, v.w});
-        }
-        return;
-    }
-    const bool want_stats = p.stats != nullptr;
-    const bool r1f32 = p.flags & SG_F_RES1_F32, r2f32 = p.flags & SG_F_RES2_F32;
-    const bool res2_same = p.res2 != nullptr && p.res2 == p.res1 && p.ldr2 == p.ldr1 && r1f32 == r2f32;
-    const int cq = min(colq, p.N - 4), mlast = p.M - 1;
-    float v[4][4];
-    {
-        float bias4[4] = {0, 0, 0, 0};
-        if (p.bias) {
-            H4 b; b.u = make_uint2(pbias.x, pbias.y);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bias4[e] = (float)b.h[e];
-        }
-        if (lnm == 1) {
-            const f32x4 lc4 = *reinterpret_cast<const f32x4*>(p.ln_c + cq), ld4 = *reinterpret_cast<const f32x4*>(p.ln_d + cq);
-            const float c4[4] = {lc4.x, lc4.y, lc4.z, lc4.w};
-            const float d4[4] = {ld4.x + bias4[0], ld4.y + bias4[1], ld4.z + bias4[2], ld4.w + bias4[3]};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float4 a = *reinterpret_cast<const float4*>(img + 4 * k * EPI_PITCH);
-                const float2 mr = *reinterpret_cast<const float2*>(xtr + 2 * (4 * k + lr));
-                const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[k][e] = fmaf(mr.y, av[e], d4[e]) - mr.x * c4[e];
-            }
-        } else if (lnm == 2) {
-            float mrx[4], mry[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float2 t = *reinterpret_cast<const float2*>(xtr + 2 * (4 * lc + e)); mrx[e] = t.x; mry[e] = t.y; }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float4 a = *reinterpret_cast<const float4*>(img + 4 * k * EPI_PITCH);
-                const float2 cd = *reinterpret_cast<const float2*>(xtr + 128 + 2 * (4 * k + lr));
-                const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[k][e] = fmaf(mry[e], av[e], cd.y + bias4[e]) - mrx[e] * cd.x;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float4 a = *reinterpret_cast<const float4*>(img + 4 * k * EPI_PITCH);
-                v[k][0] = a.x + bias4[0]; v[k][1] = a.y + bias4[1]; v[k][2] = a.z + bias4[2]; v[k][3] = a.w + bias4[3];
-            }
-        }
-    }
-    auto add_f32 = [&](const float* base, long ld) __attribute__((always_inline)) {
-        float4 t[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t[k] = *reinterpret_cast<const float4*>(base + (long)min(rowq + 4 * k, mlast) * ld + cq);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { v[k][0] += t[k].x; v[k][1] += t[k].y; v[k][2] += t[k].z; v[k][3] += t[k].w; }
-    };
-    auto add_f16 = [&](const f16* base, long ld) __attribute__((always_inline)) {
-        uint2 t[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t[k] = *reinterpret_cast<const uint2*>(base + (long)min(rowq + 4 * k, mlast) * ld + cq);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            H4 h; h.u = t[k];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[k][e] += (float)h.h[e];
-        }
-    };
-    if (p.rowbias) {
-        float4 t[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            t[k] = *reinterpret_cast<const float4*>(p.rowbias + (long)fd_div((unsigned)min(rowq + 4 * k, mlast), p.fd_rpb) * p.rowbias_ld + cq);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { v[k][0] += t[k].x; v[k][1] += t[k].y; v[k][2] += t[k].z; v[k][3] += t[k].w; }
-    }
-    if (p.res1) {
-        if (r1f32) {
-            const float w = res2_same ? 2.f : 1.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                v[k][0] = fmaf(w, pre[k].x, v[k][0]); v[k][1] = fmaf(w, pre[k].y, v[k][1]);
-                v[k][2] = fmaf(w, pre[k].z, v[k][2]); v[k][3] = fmaf(w, pre[k].w, v[k][3]);
-            }
-        } else {
-            add_f16(reinterpret_cast<const f16*>(p.res1), p.ldr1);
-            if (res2_same) add_f16(reinterpret_cast<const f16*>(p.res1), p.ldr1);
-        }
-    }
-    if (p.res2 && !res2_same) {
-        if (r2f32) add_f32(reinterpret_cast<const float*>(p.res2), p.ldr2);
-        else add_f16(reinterpret_cast<const f16*>(p.res2), p.ldr2);
-    }
-    float cs[4] = {0, 0, 0, 0}, cq2[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int gm = rowq + 4 * k;
-        if (gm < p.M && col_ok) {
-            store_out4(p, gm, colq, v[k]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { cs[e] += v[k][e]; cq2[e] = fmaf(v[k][e], v[k][e], cq2[e]); }
-        }
-    }
-    if (p.ln_out) {
-        // LayerNorm fold, producer side: (sum, M2 about the block mean) of the FINAL fp32 values per token and 64-column block.  A row of
-        // the strip lives in the 16 lanes that share lane >> 4: four exchanges per quantity, fixed order.
-        float s4[4], m4[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s4[k] = (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s4[k] += __shfl_xor(s4[k], o, 64);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float mean = s4[k] * (1.f / 64.f);
-            const float a = v[k][0] - mean, b = v[k][1] - mean, c = v[k][2] - mean, d = v[k][3] - mean;
-            m4[k] = fmaf(a, a, fmaf(b, b, fmaf(c, c, d * d)));
-        }
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) m4[k] += __shfl_xor(m4[k], o, 64);
-        if (lc == 0 && cbase < p.N) {
-            const int nblk = ((p.N >> 6) + 1) & ~1, blk = (n0 >> 6) + gn_;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int gm = rowq + 4 * k;
-                if (gm < p.M) {
-                    *reinterpret_cast<float2*>(p.ln_out + ((size_t)gm * nblk + blk) * 2) = make_float2(s4[k], m4[k]);
-                    if (p.ln_guard && !(fabsf(s4[k] * (1.f / 64.f)) + sqrtf(m4[k]) < 65504.f)) atomicOr(p.ln_guard, SG_LN_GUARD_RANGE);
+                        for (int w = 0; w < 4; ++w)
+                            s += reinterpret_cast<const float*>(smem + (g * GQ + (col >> 6)) * EPIQ_GROUP_BYTES + 64 * EPI_PITCH * 4 + w * 1024)[128 + (col & 63) * 2 + plane];
                 }
-            }
-        }
-    }
-    if (want_stats) {
-        // GroupNorm statistics: per-(tile, channel) sums of the final fp32 values.  A lane holds 4 rows of its 4 columns; the 4 lane rows
-        // are added by two exchanges, the strips of the tile (4 per group, WGM / 2 groups per column block) through LDS in fixed order.
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            cs[e] += __shfl_xor(cs[e], 16, 64); cq2[e] += __shfl_xor(cq2[e], 16, 64);
-            cs[e] += __shfl_xor(cs[e], 32, 64); cq2[e] += __shfl_xor(cq2[e], 32, 64);
-        }
-        if (lr == 0) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                xtr[128 + (4 * lc + e) * 2 + 0] = cs[e];
-                xtr[128 + (4 * lc + e) * 2 + 1] = cq2[e];
-            }
-        }
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < BN * 2; idx += NT) {
-            const int plane = idx / BN, col = idx - plane * BN;
-            const int gn = n0 + col;
-            if (gn < p.N) {
-                float s = 0.f;
-#pragma unroll
-                for (int g = 0; g < WGM / 2; ++g)
-#pragma unroll
-                    for (int w = 0; w < 4; ++w)
-                        s += reinterpret_cast<const float*>(smem + (g * GN_ + (col >> 6)) * EPIQ_GROUP_BYTES + 64 * EPI_PITCH * 4 + w * 1024)[128 + (col & 63) * 2 + plane];
-                p.stats[((size_t)(m0 / BM) * 2 + plane) * p.N + gn] = s;
+                p.stats[((size_t)(m0 / (32 * WTM * WGM)) * 2 + plane) * p.N + gn] = s;
             }
         }
     }
@@ -882,10 +743,10 @@ __global__ __launch_bounds__(256) void mma_kernel(const MmaParams p) {
         if (more) store_lds(buf ^ 1);
         __syncthreads();
     }
-    EPI_PRE_DECL;
-    epi_prefetch(p, m0, n0, wm, wn, lane, EPI_PRE_ARGS);
+    f32x4 pre_f[16]; u32x2 pre_bias;
+    epi_prefetch<16, 16>(p, m0 + wm * 64 + (lane >> 4), min(n0 + wn * 64 + 4 * (lane & 15), p.N - 4), pre_f, pre_bias);
     __syncthreads();
-    epi_finish<2, 2>(p, smem, acc, EPI_PRE_ARGS, m0, n0, z, wave, wm, wn, lane);
+    epi_finish<2, 2>(p, smem, acc, pre_f, pre_bias, m0, n0, z, wave, wm, wn, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -900,8 +761,9 @@ __global__ __launch_bounds__(256) void mma_kernel(const MmaParams p) {
 // validates that every operand ends below 2^31 elements from its base, gemm_params) to the wave-uniform LDS address `lds_wave_base` (+ lane * 16, the hardware's lane-linear image).
 // (The builtin always materialises a 64-bit per-lane address, one v_lshl_add_u64 per piece beside the MFMAs; the scalar-base form of the
 // instruction written out by hand measured negative: profiles/r06bh_lds_dma_scalar_base_form_NEGATIVE.txt.  LdsRef::a served that form
-// and nothing reads it now, but without it the compiler allocates the registers of the 4-wave kernels differently, and that code has
-// not been measured: it goes with the next change that re-measures them.)
+// and nothing reads it now.  The build without it was measured against this one (profiles/r25a_gemm_epilogue_helpers_ab.txt, section
+// 5: no register, scratch or LDS figure of any kernel differs, and it is not slower); it leaves in a commit of its own, with that
+// comparison repeated for it alone.)
 struct LdsRef { char* p; unsigned a; };          // one LDS location as a generic pointer and as its LDS byte address
 __device__ __forceinline__ LdsRef operator+(LdsRef r, int d) { return LdsRef{r.p + d, r.a + (unsigned)d}; }
 __device__ __forceinline__ LdsRef lds_ref(char* smem) {
@@ -978,7 +840,7 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
     // instead (STAGGER: conv 64^2 640->320 92.8 -> 85.5 us, 64^2 320->320 49.3 -> 47.4, 16^2 / 32^2 -2 %, profiles/r04r_*).
     constexpr bool SPREAD = (NW <= 4 || WT == 1) && !PROF, STAGGER = NW == 8 && WT == 2 && !PROF;
     static_assert(S >= 2 && S <= 8, "ring depth");
-    static_assert(WT == 2 || (WGM % 2 == 0 && WGN % 2 == 0), "32x32 waves come in 2x2 groups (epi_finish_q)");
+    static_assert(WT == 2 || (WGM % 2 == 0 && WGN % 2 == 0), "32x32 waves come in 2x2 groups (epi_finish, WT = 1)");
     static_assert((S - 1) * LPT < 64, "vmcnt is a 6-bit counter");
     static_assert(S * STAGE <= 160 * 1024, "the ring must fit the 160 KB of LDS");
     static_assert(S * STAGE <= pipe_smem_bytes<WGM, WGN, S, WT, WTM>(), "the LDS block covers the ring and the epilogue's staging regions");
@@ -1149,10 +1011,13 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
         for (int j = 0; j < WTN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    f32x4 pre_f[WT == 2 ? 16 : 4]; u32x2 pre_bias;       // prefetched epilogue operands (epi_prefetch / epi_prefetch_q)
+    constexpr int NQ = WT == 2 ? 16 : 4;
+    f32x4 pre_f[NQ]; u32x2 pre_bias;                     // prefetched epilogue operands (epi_prefetch)
     auto prefetch = [&]() __attribute__((always_inline)) {
-        if constexpr (WT == 2) epi_prefetch(p, m0, n0, wm, wn, lane, pre_f, pre_bias, WM, epi_npre<NW>());
-        else epi_prefetch_q<WGN>(p, m0, n0, wave, lane, pre_f, pre_bias);
+        // row of the lane's quad 0, its first column: the wave's sub-tile (epi_finish), or strip q of its 2x2 group's block (epi_finish, WT = 1)
+        const int rowq = (WT == 2 ? m0 + wm * WM : m0 + (wm >> 1) * 64 + ((wm & 1) * 2 + (wn & 1)) * 16) + (lane >> 4);
+        const int colq = n0 + (WT == 2 ? wn : wn >> 1) * 64 + 4 * (lane & 15);
+        epi_prefetch<NQ, epi_npre<NW, WTM>()>(p, rowq, min(colq, p.N - 4), pre_f, pre_bias);
     };
 
     // LDS offsets of this lane's fragment reads, per ring stage and k-step (the XOR swizzle makes the k-step term per-lane, and stages
@@ -1256,8 +1121,7 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
     for (int it = 0; it < nsteady; it += S) slab_seq<0, S, YS>(slab, it, nsteady);
     slab_tail<TAIL - 1, S>(slab, nt);
     if (nt <= 0) prefetch();
-    if constexpr (WT == 2) epi_finish<WGM, WGN, WTM>(p, smem, acc, pre_f, pre_bias, m0, n0, z, wave, wm, wn, lane);
-    else epi_finish_q<WGM, WGN>(p, smem, acc[0][0], pre_f, pre_bias, m0, n0, z, wave, lane);
+    epi_finish<WGM, WGN, WT, WTM>(p, smem, acc, pre_f, pre_bias, m0, n0, z, wave, wm, wn, lane);
     if constexpr (PROF) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         stamp(8);
@@ -1391,10 +1255,7 @@ __device__ __forceinline__ void epi_linear8(const MmaParams& p, int gm, int gn, 
 #pragma unroll
         for (int j = 0; j < 8; ++j) { const float d = v[j] - mean; m2 = fmaf(d, d, m2); }
         m2 += __shfl_xor(m2, 1, 64); m2 += __shfl_xor(m2, 2, 64); m2 += __shfl_xor(m2, 4, 64);
-        if ((gn & 63) == 0) {
-            *reinterpret_cast<float2*>(p.ln_out + ((size_t)gm * (((p.N >> 6) + 1) & ~1) + (gn >> 6)) * 2) = make_float2(s, m2);
-            if (p.ln_guard && !(fabsf(mean) + sqrtf(m2) < 65504.f)) atomicOr(p.ln_guard, SG_LN_GUARD_RANGE);
-        }
+        if ((gn & 63) == 0) ln_out_store(p, gm, gn >> 6, s, m2);
     }
 }
 
