@@ -5,7 +5,9 @@ Mirrors what the reference builds imperatively in
   /root/reference/model/unet_2d_blocks.py:300-372,439-489,518-586,663-709,197-267   (block ctors)
   /root/reference/model/attention.py:26-83,131-234,305-350,373-383                   (transformer ctor)
 but as plain data, so that the drop-in nn.Module (storygen_amd/model), the HIP engine
-(storygen_amd/engine.py) and the tests all agree on names, shapes and routing.
+(storygen_amd/engine.py) and the tests all agree on names, shapes and routing.  UNetArch.schedule is that routing as one flat
+list (level of every layer, skip tensor it pushes or pops): the engine's buffer sizing, its forward pass and the trainer's forward
+and backward walks loop over it instead of re-deriving it from the nested blocks.
 
 Feature ("img_dif_condition") keys are assigned by *block index* — `down_{i+1}_{j+1}`, `mid`,
 `up_{i}_{j+1}` — exactly the names the producer side uses (unet_2d_condition.py:428-429,445,468-470).
@@ -19,6 +21,7 @@ import json
 import os
 from collections import OrderedDict
 from dataclasses import dataclass, field
+from itertools import zip_longest
 from typing import Dict, List, Optional, Tuple
 
 DEFAULT_CONFIG = dict(
@@ -89,6 +92,20 @@ class BlockSpec:
     skip_channels: Tuple[int, ...] = ()        # up blocks: channels of the popped skip per layer
 
 
+@dataclass(frozen=True)
+class Step:
+    """One entry of UNetArch.schedule: a resnet layer (`resnet`, then `xf` when a transformer follows it) or a sampler conv (`sampler`)."""
+    level: int                                 # downsampling level of the input
+    out_level: int                             # ... of the output (differs for sampler convs only)
+    cout: int                                  # output channels
+    resnet: Optional[ResnetSpec] = None
+    xf: Optional[XfSpec] = None
+    sampler: Optional[str] = None              # downsamplers.0.conv / upsamplers.0.conv prefix
+    push: Optional[int] = None                 # down path: the output is skip tensor `push` of UNetArch.skips
+    pop: Optional[int] = None                  # up layers: the input is [h | skip tensor `pop`] ...
+    skip: int = 0                              # ... whose last `skip` channels are the skip (resnet.cin - skip = width of h)
+
+
 @dataclass
 class UNetArch:
     config: dict
@@ -99,13 +116,44 @@ class UNetArch:
     feature_keys: List[str]
     feature_channels: Dict[str, int]
     feature_level: Dict[str, int]              # downsampling level (0 => full latent res, 3 => /8)
+    schedule: List[Step] = field(default_factory=list)             # every layer in execution order: down path, mid, up path
+    skips: List[Tuple[int, int]] = field(default_factory=list)     # (level, channels) of the skip tensors in push order; [0] is conv_in's output
+
+    @property
+    def blocks(self) -> List[BlockSpec]:
+        return self.down + [self.mid] + self.up
 
     @property
     def resnets(self) -> List[ResnetSpec]:
         out = []
-        for b in self.down + [self.mid] + self.up:
+        for b in self.blocks:
             out.extend(b.resnets)
         return out
+
+
+def _schedule(blocks: List[BlockSpec], conv_in_channels: int) -> Tuple[List[Step], List[Tuple[int, int]]]:
+    """The walk of unet_2d_condition.py:411-475 written out once: which level every layer runs at, which skip tensor it pushes or pops."""
+    steps: List[Step] = []
+    skips, open_, lvl = [(0, conv_in_channels)], [0], 0
+
+    def push(level: int, channels: int) -> int:       # every down-path output is the next skip tensor
+        open_.append(len(skips))
+        skips.append((level, channels))
+        return open_[-1]
+
+    for blk in blocks:
+        down = blk.kind == "down"
+        for j, (r, a) in enumerate(zip_longest(blk.resnets, blk.attns)):      # (the mid block lists its one transformer only)
+            if blk.kind == "up":
+                steps.append(Step(lvl, lvl, r.cout, resnet=r, xf=a, pop=open_.pop(), skip=blk.skip_channels[j]))
+            else:
+                steps.append(Step(lvl, lvl, r.cout, resnet=r, xf=a, push=push(lvl, r.cout) if down else None))
+        if blk.sampler_prefix:
+            to = lvl + 1 if down else lvl - 1
+            steps.append(Step(lvl, to, blk.channels, sampler=blk.sampler_prefix, push=push(to, blk.channels) if down else None))
+            lvl = to
+    assert not open_ and all(skips[s.pop] == (s.level, s.skip) for s in steps if s.pop is not None), (skips, open_)
+    return steps, skips
 
 
 def build_arch(config: dict) -> UNetArch:
@@ -184,7 +232,7 @@ def build_arch(config: dict) -> UNetArch:
             blk.sampler_prefix = f"up_blocks.{i}.upsamplers.0.conv"
         up.append(blk)
 
-    return UNetArch(cfg, down, mid, up, temb_dim, fkeys, fch, flev)
+    return UNetArch(cfg, down, mid, up, temb_dim, fkeys, fch, flev, *_schedule(down + [mid] + up, boc[0]))
 
 
 def _resnet_shapes(r: ResnetSpec, temb: int, out: "OrderedDict[str, tuple]") -> None:
@@ -241,7 +289,7 @@ def param_shapes(arch: UNetArch) -> "OrderedDict[str, tuple]":
     out["time_embedding.linear_1.bias"] = (arch.temb_dim,)
     out["time_embedding.linear_2.weight"] = (arch.temb_dim, arch.temb_dim)
     out["time_embedding.linear_2.bias"] = (arch.temb_dim,)
-    for blk in arch.down + [arch.mid] + arch.up:
+    for blk in arch.blocks:
         for j, r in enumerate(blk.resnets):
             _resnet_shapes(r, arch.temb_dim, out)
         for a in blk.attns:

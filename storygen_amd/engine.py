@@ -145,7 +145,7 @@ class EngineWeights:
         self.b_temb = torch.cat(temb_b, 0).contiguous()
         self.temb_total = off
         self.xfs: Dict[str, _Xf] = {}
-        for blk in arch.down + [arch.mid] + arch.up:
+        for blk in arch.blocks:
             for a in blk.attns:
                 if a is None:
                     continue
@@ -481,24 +481,13 @@ class UNetEngine:
         # per level: widest resnet input (concat) and the level's channel count; every conv-input channel count
         cmax, cout = [0] * nlev, [0] * nlev
         conv_in_ch = [set() for _ in range(nlev)]
-        lvl = 0
-        for blk in arch.down:
-            for r in blk.resnets:
-                cmax[lvl], cout[lvl] = max(cmax[lvl], r.cin), max(cout[lvl], r.cout)
-                conv_in_ch[lvl].update((r.cin, r.cout))
-            if blk.sampler_prefix:
-                conv_in_ch[lvl].add(blk.channels)
-                lvl += 1
-        for r in arch.mid.resnets:
-            cmax[lvl], cout[lvl] = max(cmax[lvl], r.cin), max(cout[lvl], r.cout)
-            conv_in_ch[lvl].update((r.cin, r.cout))
-        for blk in arch.up:
-            for r in blk.resnets:
-                cmax[lvl], cout[lvl] = max(cmax[lvl], r.cin), max(cout[lvl], r.cout)
-                conv_in_ch[lvl].update((r.cin, r.cout))
-            if blk.sampler_prefix:
-                conv_in_ch[lvl].add(blk.channels)
-                lvl -= 1
+        for s in arch.schedule:
+            r, l = s.resnet, s.level
+            if r is None:                        # a sampler conv reads its block's output
+                conv_in_ch[l].add(s.cout)
+            else:
+                cmax[l], cout[l] = max(cmax[l], r.cin), max(cout[l], r.cout)
+                conv_in_ch[l].update((r.cin, r.cout))
         self.lv = []
         self.padded: Dict[tuple, torch.Tensor] = {}
         for l in range(nlev):
@@ -529,25 +518,12 @@ class UNetEngine:
         # torch.cat([h, skip]) (unet_2d_blocks.py:609,626,716) without a copy: every up-path resnet owns its concat input
         # buffer [M, cin] (fp32); the producer of h writes columns [0, c_h) and the skip tensor (down_block_res_samples)
         # IS the column slice [c_h, cin) of the buffer of the resnet that will pop it — the down path writes it there.
-        self.up_cats: List[torch.Tensor] = []
-        skip_views: List[torch.Tensor] = []
-        lvl = nlev - 1
-        for blk in arch.up:
-            for j, r in enumerate(blk.resnets):
-                buf = self._buf(B * self.hw[lvl], r.cin, dtype=F16 if self.fp16_resnet else F32)
-                self.up_cats.append(buf)
-                skip_views.append(buf[:, r.cin - blk.skip_channels[j]:])
-            if blk.sampler_prefix:
-                lvl -= 1
-        self.skips: List[torch.Tensor] = list(reversed(skip_views))       # skips[i] = i-th tensor the down path produces
-        self.skip_meta = [(0, boc[0])]
-        lvl = 0
-        for blk in arch.down:
-            for _ in blk.resnets:
-                self.skip_meta.append((lvl, blk.channels))
-            if blk.sampler_prefix:
-                lvl += 1
-                self.skip_meta.append((lvl, blk.channels))
+        # up_cats[-1 - i] is the buffer of the resnet that pops skip tensor i (the pops run last in, first out)
+        ups = [s for s in arch.schedule if s.pop is not None]
+        assert [s.pop for s in ups] == list(range(len(ups) - 1, -1, -1))
+        self.up_cats: List[torch.Tensor] = [self._buf(B * self.hw[s.level], s.resnet.cin, dtype=F16 if self.fp16_resnet else F32) for s in ups]
+        self.skips: List[torch.Tensor] = [buf[:, s.resnet.cin - s.skip:] for s, buf in zip(reversed(ups), reversed(self.up_cats))]       # skips[i] = i-th tensor the down path produces
+        self.skip_meta = arch.skips
         assert len(self.skips) == len(self.skip_meta)
         for sk, (l, c) in zip(self.skips, self.skip_meta):
             assert tuple(sk.shape) == (B * self.hw[l], c), (tuple(sk.shape), l, c)
@@ -719,7 +695,7 @@ class UNetEngine:
     def cache_text_kv(self):
         """Run every attn2 K / V^T projection on the current self.text_in and keep the results (use with
         forward(text_cache=True) while the prompts do not change)."""
-        for blk in self.arch.down + [self.arch.mid] + self.arch.up:
+        for blk in self.arch.blocks:
             for a in blk.attns:
                 if a is None:
                     continue
@@ -955,9 +931,10 @@ class UNetEngine:
         if harvest_only and harvest is None:
             raise ValueError("harvest_only needs a harvest plan")
         self.side = side
-        last_xf = [a for blk in self.arch.up for a in blk.attns if a is not None][-1].prefix if harvest_only else None
-        tk = dict(text_cache=text_cache)
         arch, text, skips = self.arch, self.text_in, self.skips
+        steps = list(zip(arch.schedule, arch.schedule[1:] + [None]))       # (layer, the one after it)
+        last_xf = [s.xf for s in arch.schedule if s.xf is not None][-1].prefix if harvest_only else None
+        tk = dict(text_cache=text_cache)
         skip_gn: List[_GnFeed] = [_NO_FEED]      # parallel to skips: what each skip tensor hands to a GroupNorm (conv_in: nothing)
         # --- time embedding :392-398, then all 22 time_emb_proj(silu(emb)) in one GEMV bundle.  emb is only ever consumed through
         # silu (resnet.py time_emb_proj), so the second linear writes silu(emb) once instead of every wave of the bundle redoing it
@@ -995,73 +972,37 @@ class UNetEngine:
                 self._spread(t2d, 1, 2)
             h_gn = self._xf_back(_XfPass(self, xf0, self.lv[0]["r"], r_gn, skips[1], 0, True), text_cache, shared=True)
             skip_gn.append(h_gn)
-            h, lvl, si = skips[1], 0, 2
+            h, steps = skips[1], steps[1:]
         else:
             # --- conv_in :411
             ops.conv_in(self.x_in, self.w_conv_in, self.b_conv_in, self._img(skips[0], 0))
-            h, h_gn, lvl, si = skips[0], _NO_FEED, 0, 1
-        # --- down :417-433 — every layer output is a skip tensor, so it is written straight into its skip buffer
-        for bi, blk in enumerate(arch.down):
-            for j, r in enumerate(blk.resnets):
-                if shared and bi == 0 and j == 0:
-                    continue                  # done above
-                xf, out = blk.attns[j], skips[si]
-                if xf is None:
-                    h_gn = self._resnet(self.resnets[r.prefix], h, h_gn, out, lvl)
+            h, h_gn = skips[0], _NO_FEED
+        # --- down :417-433, mid :436-445, up :448-475
+        for s, nxt in steps:
+            lvl, L = s.level, self.lv[s.level]
+            if s.push is not None:                        # every down-path output is a skip tensor: written straight into its skip buffer
+                out = skips[s.push]
+            elif nxt is not None and nxt.pop is not None:     # the h columns of the next layer's [h | skip] (the down path wrote the skip)
+                out = self.up_cats[-1 - nxt.pop][:, : nxt.resnet.cin - nxt.skip]
+            else:
+                out = L["t_out"]
+            if s.resnet is None:                          # Downsample2D / Upsample2D :656-658,730-732
+                h_gn = self._sampler_conv(s.sampler, h, out, lvl, s.out_level, down=s.out_level > lvl)
+            else:
+                rn = self.resnets[s.resnet.prefix]
+                if s.pop is not None:
+                    h, h_gn = self.up_cats[-1 - s.pop], _GnFeed.concat(h_gn, skip_gn[s.pop], s.resnet.cin)
+                if s.xf is None:
+                    h_gn = self._resnet(rn, h, h_gn, out, lvl)
                 else:
-                    rt = self.lv[lvl]["r"]
-                    r_gn = self._resnet(self.resnets[r.prefix], h, h_gn, rt, lvl, defer_out=True)
-                    h_gn = self._transformer(self.xfs[xf.prefix], rt, r_gn, out, lvl, text, harvest, consume, **tk)
-                skip_gn.append(h_gn)
-                h, si = out, si + 1
-            if blk.sampler_prefix:
-                out = skips[si]
-                h_gn = self._sampler_conv(blk.sampler_prefix, h, out, lvl, lvl + 1, down=True)
-                skip_gn.append(h_gn)
-                h, lvl, si = out, lvl + 1, si + 1
-        assert si == len(skips) == len(skip_gn)
-        # --- mid :436-445
-        L = self.lv[lvl]
-        m0, m1 = arch.mid.resnets
-        r_gn = self._resnet(self.resnets[m0.prefix], h, h_gn, L["r"], lvl, defer_out=True)
-        h_gn = self._transformer(self.xfs[arch.mid.attns[0].prefix], L["r"], r_gn, L["t_out"], lvl, text, harvest, consume, **tk)
-        blk0 = arch.up[0]
-        k = 0                                                                              # index of the up-path resnet
-        cat = self.up_cats[k]
-        h_gn = self._resnet(self.resnets[m1.prefix], L["t_out"], h_gn, cat[:, : blk0.resnets[0].cin - blk0.skip_channels[0]], lvl)
-        # --- up :448-475 — `cat` = [h | skip]: h was written by the previous layer, the skip by the down path
-        for bi, blk in enumerate(arch.up):
-            L = self.lv[lvl]
-            nres = len(blk.resnets)
-            for j, r in enumerate(blk.resnets):
-                si -= 1
-                assert cat.shape[1] == r.cin and skips[si].data_ptr() == cat[:, r.cin - blk.skip_channels[j]:].data_ptr()
-                cat_gn = _GnFeed.concat(h_gn, skip_gn.pop(), r.cin)
-                if j + 1 < nres:
-                    nxt = self.up_cats[k + 1]
-                    out = nxt[:, : blk.resnets[j + 1].cin - blk.skip_channels[j + 1]]
-                else:
-                    nxt, out = None, L["t_out"]
-                xf = blk.attns[j]
-                if xf is None:
-                    h_gn = self._resnet(self.resnets[r.prefix], cat, cat_gn, out, lvl)
-                else:
-                    r_gn = self._resnet(self.resnets[r.prefix], cat, cat_gn, L["r"], lvl, defer_out=True)
-                    if xf.prefix == last_xf:      # harvest_only: the pass ends with its last feature (before that block's text projections)
-                        self._xf_to_harvest(_XfPass(self, self.xfs[xf.prefix], L["r"], r_gn, None, lvl, consume), harvest)
+                    r_gn = self._resnet(rn, h, h_gn, L["r"], lvl, defer_out=True)
+                    if s.xf.prefix == last_xf:      # harvest_only: the pass ends with its last feature (before that block's text projections)
+                        self._xf_to_harvest(_XfPass(self, self.xfs[s.xf.prefix], L["r"], r_gn, None, lvl, consume), harvest)
                         return None
-                    h_gn = self._transformer(self.xfs[xf.prefix], L["r"], r_gn, out, lvl, text, harvest, consume, **tk)
-                k += 1
-                if nxt is not None:
-                    cat = nxt
-                h = out
-            if blk.sampler_prefix:                                                        # Upsample2D :656-658,730-732
-                nblk = arch.up[bi + 1]
-                cat = self.up_cats[k]
-                c_h = nblk.resnets[0].cin - nblk.skip_channels[0]
-                h_gn = self._sampler_conv(blk.sampler_prefix, h, cat[:, :c_h], lvl, lvl - 1, down=False)
-                lvl -= 1
-        assert si == 0 and lvl == 0
+                    h_gn = self._transformer(self.xfs[s.xf.prefix], L["r"], r_gn, out, lvl, text, harvest, consume, **tk)
+            if s.push is not None:
+                skip_gn.append(h_gn)
+            h = out
         # --- out :477-480
         L = self.lv[0]
         ops.groupnorm(h.unflatten(0, (self.B, self.hw[0])), *self.gn_out, L["gn"].unflatten(0, (self.B, self.hw[0])),

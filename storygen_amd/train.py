@@ -114,7 +114,7 @@ class UNetTrainer:
         self.trainable = trainable
         self.ref_levels = "stage2"      # noise level of reference frame i: ref_t * (3 - i) (stage 2, :311) or ref_t for all ("coco", train_COCO.py:303)
         self.xfs = {a.prefix: Transformer2DTrain(sd, a, self.groups, device, trainable)
-                    for blk in arch.down + [arch.mid] + arch.up for a in blk.attns if a is not None}
+                    for blk in arch.blocks for a in blk.attns if a is not None}
         self.samplers = {}
         for blk in arch.down + arch.up:
             if blk.sampler_prefix:
@@ -354,52 +354,27 @@ class UNetTrainer:
         ops.timestep_embed(t.to(dev, F32).contiguous(), wts.freqs, temb0, self.cfg["flip_sin_to_cos"])
         ops.linear_rows(temb0, wts.w_t1, wts.b_t1, temb1, act_out=True)
         ops.linear_rows(temb1, wts.w_t2, wts.b_t2, temb2, act_out=True)     # emb is only consumed as silu(emb) (resnet.py time_emb_proj)
-        tape: List[tuple] = []
-        hh, ww = H, W
 
-        def resnet(prefix, x):
+        def resnet(prefix, x, hh, ww):
             w, b = self.temb_proj[prefix]
             tp = ops.linear_rows(temb2, w, b, _e(B, w.shape[0], dev=dev, dtype=F32))
-            tape.append(("resnet", prefix))
             return self.resnets[prefix].forward(x, tp, B, hh, ww)
-
-        def xf(spec, x):
-            tape.append(("xf", spec.prefix))
-            return self.xfs[spec.prefix].forward(x, text16, None if ctx16 is None else ctx16[spec.feature_key], B)
 
         h = _e(B * H * W, boc0, dev=dev, dtype=F32)
         ops.conv_in(noisy, wts.w_conv_in, wts.b_conv_in, h.view(B, H, W, boc0))
-        tape.append(("conv_in",))
         skips = [h]
-        for blk in arch.down:
-            for j, r in enumerate(blk.resnets):
-                h = resnet(r.prefix, h)
-                if blk.attns[j] is not None:
-                    h = xf(blk.attns[j], h)
+        for s in arch.schedule:
+            hh, ww = H >> s.level, W >> s.level
+            if s.resnet is None:
+                h = (self._down if s.out_level > s.level else self._up)(s.sampler, h, hh, ww)
+            else:
+                if s.pop is not None:
+                    h = torch.cat([h, skips.pop()], dim=1)                           # unet_2d_blocks.py:609,626,716
+                h = resnet(s.resnet.prefix, h, hh, ww)
+                if s.xf is not None:
+                    h = self.xfs[s.xf.prefix].forward(h, text16, None if ctx16 is None else ctx16[s.xf.feature_key], B)
+            if s.push is not None:
                 skips.append(h)
-                tape.append(("skip_push",))
-            if blk.sampler_prefix:
-                tape.append(("down", blk.sampler_prefix, hh // 2, ww // 2))
-                h = self._down(blk.sampler_prefix, h, hh, ww)
-                hh, ww = hh // 2, ww // 2
-                skips.append(h)
-                tape.append(("skip_push",))
-        m0, m1 = arch.mid.resnets
-        h = resnet(m0.prefix, h)
-        h = xf(arch.mid.attns[0], h)
-        h = resnet(m1.prefix, h)
-        for blk in arch.up:
-            for j, r in enumerate(blk.resnets):
-                s = skips.pop()
-                tape.append(("cat", h.shape[1]))
-                h = torch.cat([h, s], dim=1)                                         # unet_2d_blocks.py:609,626,716
-                h = resnet(r.prefix, h)
-                if blk.attns[j] is not None:
-                    h = xf(blk.attns[j], h)
-            if blk.sampler_prefix:
-                tape.append(("up", blk.sampler_prefix, hh, ww))
-                h = self._up(blk.sampler_prefix, h, hh, ww)
-                hh, ww = 2 * hh, 2 * ww
         x_out = h
         hw = H * W
         ws = _e(ops.groupnorm_workspace_bytes(B, self.groups), dev=dev, dtype=torch.uint8)
@@ -407,7 +382,7 @@ class UNetTrainer:
         ops.groupnorm(x_out.view(B, hw, boc0), *self.gn_out, gn.view(B, hw, boc0), self.groups, self.eps, True, ws)
         pred = _e(B, self.cfg["out_channels"], H, W, dev=dev, dtype=F32)
         ops.conv_out(gn.view(B, H, W, boc0), self.w_conv_out, self.b_conv_out, pred)
-        self._tape, self._x_out = tape, x_out
+        self._x_out = x_out
         return pred
 
     def backward_main(self, d_pred: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -432,7 +407,7 @@ class UNetTrainer:
 
     def _backward_scaled(self, d_pred: torch.Tensor) -> Dict[str, torch.Tensor]:
         dev, B, H, W = self.dev, self.B, self.H, self.W
-        tape, x_out = self._tape, self._x_out
+        sched, x_out = self.arch.schedule, self._x_out
         boc0 = self.cfg["block_out_channels"][0]
         hw = H * W
         # ---- backward (oracle.storygen_backward.unet_backward)
@@ -444,27 +419,25 @@ class UNetTrainer:
                           True, ws)
         grads: Dict[str, torch.Tensor] = {}
         pending: List[torch.Tensor] = []
-        n_xf = sum(1 for rec in tape if rec[0] == "xf")
-        for rec in reversed(tape):
-            kind = rec[0]
-            if kind == "up":
-                dh = self._up_bwd(rec[1], dh, rec[2], rec[3])
-            elif kind == "cat":
-                pending.append(dh[:, rec[1]:].contiguous())
-                dh = dh[:, : rec[1]].contiguous()
-            elif kind == "resnet":
-                dh = self.resnets[rec[1]].backward(dh)
-            elif kind == "xf":
-                dh, g = self.xfs[rec[1]].backward(dh)
-                grads.update(g)
-                if len(grads) == 5 * n_xf:
-                    break                                      # nothing trainable below the first transformer block
-            elif kind == "skip_push":
+        n_xf = sum(1 for s in sched if s.xf is not None)
+        for s in reversed(sched):                              # each layer's forward, undone back to front
+            if s.push is not None:
                 dh = dh + pending.pop()
-            elif kind == "down":
-                dh = self._down_bwd(rec[1], dh, rec[2], rec[3])
-            elif kind == "conv_in":
-                break
+            if s.resnet is None and s.out_level > s.level:
+                dh = self._down_bwd(s.sampler, dh, H >> s.out_level, W >> s.out_level)
+            elif s.resnet is None:
+                dh = self._up_bwd(s.sampler, dh, H >> s.level, W >> s.level)
+            else:
+                if s.xf is not None:
+                    dh, g = self.xfs[s.xf.prefix].backward(dh)
+                    grads.update(g)
+                    if len(grads) == 5 * n_xf:
+                        break                                  # nothing trainable below the first transformer block
+                dh = self.resnets[s.resnet.prefix].backward(dh)
+                if s.pop is not None:                          # [h | skip]: the skip's share waits for the layer that pushed it
+                    c_h = s.resnet.cin - s.skip
+                    pending.append(dh[:, c_h:].contiguous())
+                    dh = dh[:, :c_h].contiguous()
         return grads
 
 
