@@ -662,6 +662,46 @@ int sg_clip_patchify_u8(const uint8_t* x, int64_t bsx, int64_t ldx, int32_t N, i
                         const int32_t* vbounds, sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Aligning story frames with narration (data_process/align.py:22-30,127-159): the cost matrix of r frame features against c sentence
+ * features, and dynamic time warping over it with the backtrace, one launch each.  Nothing but the path has to reach the host.
+ *
+ * sg_align_cost_f64: frames fp32 [r, dim] (row stride ldf in elements), sents fp32 [c, dim] (contiguous), frame_times [r] and
+ *   sent_times [c] float64 seconds -> cost float64 [r, c] (row stride ldo).  Per cell, all in float64:
+ *     dot = sum_k f[k] s[k];  nf = sum_k f[k]^2;  ns = sum_k s[k]^2        (a product of two fp32 values is exact in float64)
+ *     cd  = 1 - dot / (sqrt(nf) sqrt(ns) + 1e-9)                            (align.py:22-25, on features that are NOT normalised)
+ *     dt  = |frame_times[i] - sent_times[j]|
+ *     cost[i, j] = cd  if dt <= 60,  floor(dt / 60) + cd  otherwise         (align.py:137-140)
+ *   A zero feature row gives cd = 1 (0 / 1e-9).  One wave per cell, lanes striding over dim; the three sums are added in float64 in a
+ *   fixed order (per-lane chains, then a butterfly), no atomics, no workspace: each errs by at most (dim - 1) 2^-53 sum |terms|.
+ *   The script's fp16 features and fp16 NumPy cosine are not reproduced: features are the engines' fp32 outputs.
+ *   SG_EINVAL before any launch: a null pointer, r or c outside [1, SG_DTW_MAX_SIDE], r * c >= 2^31, dim < 1, ldf < dim, ldo < c.
+ *
+ * sg_dtw_path_f64: cost float64 [r, c] (row stride ldc) ->
+ *     acc[i, j]   = cost[i, j] + min(acc[i-1, j-1], acc[i-1, j], acc[i, j-1])        float64 [r, c] (row stride lda); may be NULL
+ *                   with acc[-1, -1] = 0 and every other cell outside the matrix +inf  (align.py:130-145)
+ *     codes[i, j] = which of the three was taken, uint8 [r, c] contiguous: 0 diagonal, 1 up (i - 1), 2 left (j - 1); the FIRST minimum
+ *                   in that order wins (m = diagonal; if up < m take up; if left < m take left: numpy's argmin of the triple,
+ *                   align.py:150).  Row 0 is forced to 2 and column 0 to 1 ((0, 0): 0), which is what the rule gives on finite costs.
+ *     path        = int32 [r + c - 1, 2], entries [0, path_len) written: the walk along the codes from (r - 1, c - 1) while i > 0 or
+ *                   j > 0, stored in forward order, (0, 0) first (align.py:147-159).  path_len int32 [1].
+ *   The triple the backtrace inspects at (i, j) is the triple the fill read there, so the walk follows codes and reads no float.
+ *   One workgroup of SG_DTW_THREADS walks the anti-diagonals i + j = 0 .. r + c - 2: threads stride over a diagonal's cells, the last
+ *   two diagonals stay in LDS as float64 under the cell's coordinate along the shorter side, one barrier per diagonal.  Then one lane
+ *   follows the codes; in row 0 it steps left and in column 0 up without looking, and it makes at most r + c - 2 moves: +-inf or NaN
+ *   costs give a wrong path, never a position outside the matrix, never an unbounded loop, never path_len > r + c - 1.
+ *   Nothing outside path[0, path_len), path_len, and the [r, c] windows of codes and acc is written.
+ *   Limits (3 diagonals of float64 in 48 KiB of LDS; 16-bit coordinates in the walk's notes): min(r, c) <= SG_DTW_MAX_SHORT,
+ *   r, c <= SG_DTW_MAX_SIDE, r * c < 2^31.  SG_EINVAL before any launch beyond them, and for a null cost / codes / path / path_len,
+ *   r or c < 1, ldc < c, lda < c with acc given. */
+#define SG_DTW_THREADS 256
+#define SG_DTW_MAX_SHORT 2048
+#define SG_DTW_MAX_SIDE 65535
+int sg_align_cost_f64(const float* frames, int64_t ldf, const float* sents, const double* frame_times, const double* sent_times,
+                      double* cost, int64_t ldo, int32_t r, int32_t c, int32_t dim, sg_stream_t stream);
+int sg_dtw_path_f64(const double* cost, int64_t ldc, int32_t r, int32_t c, uint8_t* codes, double* acc, int64_t lda, int32_t* path,
+                    int32_t* path_len, sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimizer step of the training loop: /root/reference/train_StorySalon_stage2.py:186-205 builds torch.optim.AdamW
  * or bitsandbytes' AdamW8bit over the trainable (attn3) parameters, :328-333 clips the global gradient norm and steps.
  *

@@ -1158,6 +1158,91 @@ def clip_patchify_u8(x_u8: torch.Tensor, out: torch.Tensor, S: int, ps: int, mea
     return out
 
 
+# SG_DTW_*: limits of sg_align_cost_f64 / sg_dtw_path_f64 (include/storygen_hip.h)
+DTW_MAX_SHORT, DTW_MAX_SIDE = 2048, 65535
+
+
+def _f64(t: torch.Tensor, name: str):
+    if t.dtype != torch.float64 or not t.is_cuda:
+        raise TypeError(f"{name}: expected a CUDA/HIP float64 tensor, got {t.dtype} on {t.device}")
+
+
+def _same_device(who: str, first: torch.Tensor, **others) -> None:
+    """Every tensor of one launch lives on one device: a pointer of another GPU would be read as an address of this one."""
+    for name, t in others.items():
+        if t is not None and t.device != first.device:
+            raise ValueError(f"{who}: {name} is on {t.device}, the first operand on {first.device}")
+
+
+def check_align_sides(who: str, r: int, c: int, dtw: bool) -> None:
+    if r < 1 or c < 1:
+        raise ValueError(f"{who}: r = {r}, c = {c}: at least one frame and one sentence")
+    if r > DTW_MAX_SIDE or c > DTW_MAX_SIDE or r * c >= 2 ** 31:
+        raise ValueError(f"{who}: r = {r}, c = {c} exceed the limits (each side <= {DTW_MAX_SIDE}, r * c < 2^31)")
+    if dtw and min(r, c) > DTW_MAX_SHORT:
+        raise ValueError(f"{who}: the shorter side min({r}, {c}) exceeds {DTW_MAX_SHORT}")
+
+
+def align_cost(frame_feats: torch.Tensor, sent_feats: torch.Tensor, frame_times: torch.Tensor, sent_times: torch.Tensor,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frame_feats fp32 [r, dim] (any row stride), sent_feats fp32 [c, dim] (contiguous), frame_times [r] and sent_times [c] float64 seconds
+    -> cost float64 [r, c]: cosine distance 1 - f.s / (|f| |s| + 1e-9) in float64, plus floor(dt / 60) where the two times are more than
+    60 s apart (sg_align_cost_f64; data_process/align.py:22-30,137-140).  `out`, when given, may be a window of a larger buffer."""
+    _f32(frame_feats, "frame_feats"), _f32(sent_feats, "sent_feats"), _f64(frame_times, "frame_times"), _f64(sent_times, "sent_times")
+    if frame_feats.dim() != 2 or sent_feats.dim() != 2 or frame_feats.shape[1] != sent_feats.shape[1]:
+        raise ValueError(f"align_cost: features must be [r, dim] and [c, dim], got {tuple(frame_feats.shape)} and {tuple(sent_feats.shape)}")
+    (r, dim), c = frame_feats.shape, sent_feats.shape[0]
+    check_align_sides("align_cost", r, c, dtw=False)
+    if dim < 1:
+        raise ValueError("align_cost: dim must be at least 1")
+    if tuple(frame_times.shape) != (r,) or tuple(sent_times.shape) != (c,):
+        raise ValueError(f"align_cost: times must be [{r}] and [{c}], got {tuple(frame_times.shape)} and {tuple(sent_times.shape)}")
+    if not (sent_feats.is_contiguous() and frame_times.is_contiguous() and sent_times.is_contiguous()):
+        raise ValueError("align_cost: sent_feats, frame_times and sent_times must be contiguous")
+    if out is None:
+        out = torch.empty(r, c, dtype=torch.float64, device=frame_feats.device)
+    _f64(out, "out")
+    if tuple(out.shape) != (r, c):
+        raise ValueError(f"align_cost: out must be [{r}, {c}], got {tuple(out.shape)}")
+    _same_device("align_cost", frame_feats, sent_feats=sent_feats, frame_times=frame_times, sent_times=sent_times, out=out)
+    check(lib.sg_align_cost_f64(frame_feats.data_ptr(), _row_stride(frame_feats, "frame_feats"), sent_feats.data_ptr(), frame_times.data_ptr(),
+                                sent_times.data_ptr(), out.data_ptr(), _row_stride(out, "out"), r, c, dim, _stream()), "sg_align_cost_f64")
+    return out
+
+
+def dtw_path(cost: torch.Tensor, return_acc: bool = False, *, path: Optional[torch.Tensor] = None, path_len: Optional[torch.Tensor] = None,
+             codes: Optional[torch.Tensor] = None, acc: Optional[torch.Tensor] = None):
+    """cost float64 [r, c] (any row stride) -> (path int32 [r + c - 1, 2] of which the first path_len rows are written, path_len int32 [1],
+    codes uint8 [r, c]), all on the device, plus the accumulated matrix acc float64 [r, c] with return_acc (sg_dtw_path_f64: the recurrence
+    and the first-minimum backtrace of data_process/align.py:130-159, the path from (0, 0) to (r - 1, c - 1)).  Outputs are allocated when
+    not given; a given acc may be a window of a larger buffer, the others are contiguous."""
+    _f64(cost, "cost")
+    if cost.dim() != 2:
+        raise ValueError(f"dtw_path: cost must be [r, c], got {tuple(cost.shape)}")
+    r, c = cost.shape
+    check_align_sides("dtw_path", r, c, dtw=True)
+    dev = cost.device
+    path = torch.empty(r + c - 1, 2, dtype=torch.int32, device=dev) if path is None else path
+    path_len = torch.empty(1, dtype=torch.int32, device=dev) if path_len is None else path_len
+    codes = torch.empty(r, c, dtype=torch.uint8, device=dev) if codes is None else codes
+    if acc is None and return_acc:
+        acc = torch.empty(r, c, dtype=torch.float64, device=dev)
+    for t, name, dtype, shape in ((path, "path", torch.int32, (r + c - 1, 2)), (path_len, "path_len", torch.int32, (1,)),
+                                  (codes, "codes", torch.uint8, (r, c))):
+        if t.dtype != dtype or not t.is_cuda:
+            raise TypeError(f"{name}: expected a CUDA/HIP {dtype} tensor, got {t.dtype} on {t.device}")
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"dtw_path: {name} must be contiguous {shape}, got {tuple(t.shape)}")
+    if acc is not None:
+        _f64(acc, "acc")
+        if tuple(acc.shape) != (r, c):
+            raise ValueError(f"dtw_path: acc must be [{r}, {c}], got {tuple(acc.shape)}")
+    _same_device("dtw_path", cost, path=path, path_len=path_len, codes=codes, acc=acc)
+    check(lib.sg_dtw_path_f64(cost.data_ptr(), _row_stride(cost, "cost"), r, c, codes.data_ptr(), _p(acc),
+                              0 if acc is None else _row_stride(acc, "acc"), path.data_ptr(), path_len.data_ptr(), _stream()), "sg_dtw_path_f64")
+    return (path, path_len, codes, acc) if acc is not None else (path, path_len, codes)
+
+
 # ------------------------------------------------------------------------------------------------ backward pass (config 4)
 # Validated on MI355X in round 2 (tests/test_backward_gpu.py).  Kernels: csrc/backward.hip, attention_bwd.hip; formulas: oracle/storygen_backward.py.
 def layernorm_bwd(x: torch.Tensor, dy1: torch.Tensor, g1: torch.Tensor, out: torch.Tensor, eps: float = 1e-5,
