@@ -702,6 +702,35 @@ int sg_dtw_path_f64(const double* cost, int64_t ldc, int32_t r, int32_t c, uint8
                     int32_t* path_len, sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Removing near-duplicate keyframes (data_process/dup_remove.py:21-46): the cosine similarity of every frame's feature with the
+ * feature of the frame before it, and the script's decision per pair, in one launch.  Only sim and drop have to reach the host.
+ *
+ * sg_adjacent_cosine_f64: feats fp32 [N, dim] (row stride ldf in elements), frames in the script's order ->
+ *     sim[0]  = 0.0                      the script compares the first frame with a zero feature; torch.cosine_similarity gives
+ *                                        exactly 0 there (a zero numerator over eps * max(|f|, eps))
+ *     sim[i]  = dot(f_i, f_{i-1}) / (max(|f_i|, eps) * max(|f_{i-1}|, eps))        i >= 1, float64 [N]
+ *               dot = sum_k f_i[k] f_{i-1}[k];  |f|^2 = sum_k f[k]^2                (a product of two fp32 values is exact in float64)
+ *     drop[i] = 1 iff i + 1 < N and sim[i + 1] >= threshold, else 0               uint8 [N]
+ *   dup_remove.py:38-46 removes the PREVIOUS file when the current frame is similar to it, and pre_feature advances whether or not
+ *   that file was removed: the decisions are independent per pair, and the last frame is always kept.  A NaN similarity (a NaN or
+ *   infinite feature) compares false and keeps the frame.  Two zero rows give 0 (0 / eps^2; NaN where eps = 0).
+ *   Deliberately different from the script: it compares `similarity.item()` of a float32 cosine with 0.75; here the cosine and the
+ *   comparison are float64 on the fp32 features, so a pair whose float32 cosine rounds across the threshold may be decided the
+ *   other way (the exact tie stays a tie: it drops).
+ *   One wave of 64 per frame i, four waves per workgroup.  Lanes stride over dim: four consecutive floats per lane and step
+ *   (16-byte loads) where feats is 16-byte aligned and ldf % 4 == 0, the columns past the last whole four and every other layout
+ *   one float per lane and step.  The three sums are added in float64 in a fixed order (per-lane chains, then a butterfly over
+ *   the lane distances 32 .. 1), no atomics: each errs by at most (dim - 1) 2^-53 sum |terms|.  Lane 0 writes sim[i] and, for
+ *   i >= 1, drop[i - 1]; the wave of frame N - 1 also writes drop[N - 1] = 0: every output element is written exactly once and
+ *   nothing else is written.  No LDS, no workspace, no private segment.
+ *   Limits: 1 <= N <= SG_DEDUP_MAX_FRAMES, 1 <= dim <= SG_DEDUP_MAX_DIM, dim <= ldf <= 2^40.  SG_EINVAL before any launch beyond
+ *   them, and for a null pointer, sim and drop overlapping each other, eps negative or NaN. */
+#define SG_DEDUP_MAX_FRAMES 1048576
+#define SG_DEDUP_MAX_DIM 65536
+int sg_adjacent_cosine_f64(const float* feats, int64_t ldf, int32_t N, int32_t dim, double eps, double threshold, double* sim,
+                           uint8_t* drop, sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimizer step of the training loop: /root/reference/train_StorySalon_stage2.py:186-205 builds torch.optim.AdamW
  * or bitsandbytes' AdamW8bit over the trainable (attn3) parameters, :328-333 clips the global gradient norm and steps.
  *

@@ -251,6 +251,8 @@ SIGNATURES = {
                                     C.c_int32, C.c_void_p]),
     "sg_dtw_path_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "sg_adjacent_cosine_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "sg_sumsq_scratch_floats": (C.c_size_t, []),
     "sg_sumsq_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sg_adamw_f32": (C.c_int, [C.POINTER(AdamWDesc), C.c_void_p]),

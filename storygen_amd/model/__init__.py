@@ -7,3 +7,4 @@ from .unet_2d_condition import UNet2DConditionModel, UNet2DConditionOutput  # no
 from .pipeline import StableDiffusionPipeline, StableDiffusionPipelineOutput  # noqa: F401
 from .attention_processor import HipCrossAttnProcessor  # noqa: F401
 from .encoders import AutoencoderKL, CLIPModel, CLIPTextModel, CLIPVisionModelWithProjection  # noqa: F401
+from .dino import DinoVisionTransformer  # noqa: F401  (data_process/dup_remove.py's dino_vitb8)

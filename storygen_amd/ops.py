@@ -1243,6 +1243,63 @@ def dtw_path(cost: torch.Tensor, return_acc: bool = False, *, path: Optional[tor
     return (path, path_len, codes, acc) if acc is not None else (path, path_len, codes)
 
 
+# SG_DEDUP_*: limits of sg_adjacent_cosine_f64 (include/storygen_hip.h)
+DEDUP_MAX_FRAMES, DEDUP_MAX_DIM = 1 << 20, 65536
+DEDUP_IMAGE_MEAN = (0.485, 0.456, 0.406)                    # Normalize() of data_process/dup_remove.py:13 (the ImageNet constants)
+DEDUP_IMAGE_STD = (0.229, 0.224, 0.225)
+
+
+def dedup_u8_geometry(h: int, w: int, S: int, resize: int = 256) -> tuple:
+    """(resized H, resized W, top, left) of dup_remove.py's Resize(resize) + CenterCrop(S) on an h x w image (host only): the shorter side
+    becomes `resize`, the longer int(resize * long / short) (clip_resize_geometry(h, w, resize)'s resized sizes); the crop's offset per axis
+    is int(round((size - S) / 2.0)), halves to the even integer (torchvision's CenterCrop).  A resized side below S is refused: the script
+    would pad it."""
+    Hr, Wr, _, _ = clip_resize_geometry(h, w, resize)
+    if min(Hr, Wr) < S:
+        raise ValueError(f"dedup_u8_geometry: a {h} x {w} frame resized to {Hr} x {Wr} is smaller than the {S} x {S} crop (padding is out of scope)")
+    return Hr, Wr, int(round((Hr - S) / 2.0)), int(round((Wr - S) / 2.0))
+
+
+def check_dedup_sides(who: str, N: int, dim: int) -> None:
+    if N < 1 or N > DEDUP_MAX_FRAMES:
+        raise ValueError(f"{who}: {N} frames are outside [1, {DEDUP_MAX_FRAMES}]")
+    if dim < 1 or dim > DEDUP_MAX_DIM:
+        raise ValueError(f"{who}: feature dim {dim} is outside [1, {DEDUP_MAX_DIM}]")
+
+
+def adjacent_cosine(feats: torch.Tensor, threshold: float = 0.75, eps: float = 1e-8, sim: Optional[torch.Tensor] = None,
+                    drop: Optional[torch.Tensor] = None) -> tuple:
+    """feats fp32 [N, dim] (any row stride), frames in order -> (sim float64 [N], drop uint8 [N]) on the device: sim[0] = 0, sim[i] the
+    float64 cosine similarity of frame i with frame i - 1 under torch.cosine_similarity's clamp of each norm at eps; drop[i] = 1 iff
+    i + 1 < N and sim[i + 1] >= threshold — the files data_process/dup_remove.py:38-46 deletes (sg_adjacent_cosine_f64, one launch).
+    sim and drop, when given, are contiguous [N] tensors and may be windows of larger buffers."""
+    _f32(feats, "feats")
+    if feats.dim() != 2:
+        raise ValueError(f"adjacent_cosine: feats must be [N, dim], got {tuple(feats.shape)}")
+    N, dim = feats.shape
+    check_dedup_sides("adjacent_cosine", N, dim)
+    eps, threshold = float(eps), float(threshold)
+    if not eps >= 0.0:
+        raise ValueError(f"adjacent_cosine: eps = {eps} must be a number >= 0")
+    ldf = _row_stride(feats, "feats")
+    if N == 1:
+        ldf = max(ldf, dim)                                  # (the stride of a single row is never used)
+    if ldf < dim:
+        raise ValueError(f"adjacent_cosine: feats rows overlap (row stride {ldf} below dim {dim})")
+    sim = torch.empty(N, dtype=torch.float64, device=feats.device) if sim is None else sim
+    drop = torch.empty(N, dtype=torch.uint8, device=feats.device) if drop is None else drop
+    _f64(sim, "sim")
+    if drop.dtype != torch.uint8 or not drop.is_cuda:
+        raise TypeError(f"drop: expected a CUDA/HIP uint8 tensor, got {drop.dtype} on {drop.device}")
+    for t, name in ((sim, "sim"), (drop, "drop")):
+        if tuple(t.shape) != (N,) or not t.is_contiguous():
+            raise ValueError(f"adjacent_cosine: {name} must be contiguous [{N}], got {tuple(t.shape)}")
+    _same_device("adjacent_cosine", feats, sim=sim, drop=drop)
+    check(lib.sg_adjacent_cosine_f64(feats.data_ptr(), ldf, N, dim, eps, threshold, sim.data_ptr(), drop.data_ptr(), _stream()),
+          "sg_adjacent_cosine_f64")
+    return sim, drop
+
+
 # ------------------------------------------------------------------------------------------------ backward pass (config 4)
 # Validated on MI355X in round 2 (tests/test_backward_gpu.py).  Kernels: csrc/backward.hip, attention_bwd.hip; formulas: oracle/storygen_backward.py.
 def layernorm_bwd(x: torch.Tensor, dy1: torch.Tensor, g1: torch.Tensor, out: torch.Tensor, eps: float = 1e-5,
