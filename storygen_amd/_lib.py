@@ -312,7 +312,13 @@ def load() -> C.CDLL:
     return lib
 
 
+class InvalidArgument(RuntimeError, ValueError):
+    """The library refused the arguments on the host, before anything was enqueued (SG_EINVAL: shape, alignment, range; SG_EUNSUP: a
+    valid request no kernel is built for).  A ValueError like the refusals of the wrappers in ops.py, so a caller catches both alike,
+    and still the RuntimeError that every failure of the library has always been."""
+
+
 def check(code: int, what: str = "") -> None:
     if code != 0:
         msg = load().sg_last_error().decode(errors="replace")
-        raise RuntimeError(f"libstorygen_hip {what} failed ({code}): {msg}")
+        raise (InvalidArgument if code in (-1, -2) else RuntimeError)(f"libstorygen_hip {what} failed ({code}): {msg}")

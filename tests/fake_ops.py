@@ -10,13 +10,11 @@ import math
 import torch
 import torch.nn.functional as F
 
-EPI_LINEAR, EPI_GEGLU = 0, 1
+# one body per op: the entry points the encoder stand-ins have too live in tests/ops_emulation.py
+from tests.ops_emulation import (EPI_GEGLU, EPI_LINEAR, _store, conv3x3, conv_in, conv_out, copy_rows, gemm, groupnorm, layernorm,  # noqa: F401
+                                 pad_cast)
+
 LOG2E = 1.4426950408889634
-
-
-def _store(out, val):
-    out.copy_(val.to(out.dtype))
-    return out
 
 
 def gemm_workspace_bytes(M, N, split_k=0):
@@ -29,32 +27,6 @@ def groupnorm_workspace_bytes(B, groups):
 
 def groupnorm_bwd_workspace_bytes(B, groups):
     return 16
-
-
-def gemm(a, w, out, *, bias=None, rowbias=None, rows_per_batch=1, res1=None, res2=None, epilogue=EPI_LINEAR, split_k=0,
-         workspace=None, out2=None, tile=None):
-    v = a.float() @ w.float().t()
-    if bias is not None:
-        v = v + bias.float()
-    if epilogue == EPI_GEGLU:      # columns come in blocks of 64: 32 values then their 32 gates -> val * gelu(gate)
-        M, N = v.shape
-        v = v.view(M, N // 64, 2, 32)
-        v = (v[:, :, 0] * F.gelu(v[:, :, 1])).reshape(M, N // 2)
-    else:
-        if res1 is not None:
-            v = v + res1.float()
-        if res2 is not None:
-            v = v + res2.float()
-    if out2 is not None:
-        _store(out2, v)
-    return _store(out, v)
-
-
-def layernorm(x, g1, b1, y1, eps=1e-5, g2=None, b2=None, y2=None):
-    C = x.shape[-1]
-    _store(y1, F.layer_norm(x.float(), (C,), g1.float(), b1.float(), eps))
-    if y2 is not None:
-        _store(y2, F.layer_norm(x.float(), (C,), g2.float(), b2.float(), eps))
 
 
 def _heads(t, H):
@@ -112,17 +84,6 @@ def _gn(x, gamma, beta, groups, eps, silu):
     return (F.silu(y) if silu else y).transpose(1, 2)
 
 
-def groupnorm(x, gamma, beta, out, groups, eps, silu, workspace, xcopy=None):
-    y = _gn(x, gamma, beta, groups, eps, silu)
-    if xcopy is not None:
-        _store(xcopy, x)
-    if out.dim() == 4:                                       # zero-bordered image: interior only
-        B, Hp, Wp, C = out.shape
-        out[:, 1:-1, 1:-1] = y.reshape(B, Hp - 2, Wp - 2, C).to(out.dtype)
-        return out
-    return _store(out, y)
-
-
 def groupnorm_bwd(x, dy, gamma, beta, out, groups, eps, silu, workspace, res=None):
     xr = x.float().detach().requires_grad_(True)
     with torch.enable_grad():
@@ -160,37 +121,6 @@ def geglu_bwd(proj_il, du, dproj_il):
     return _store(dproj_il, torch.stack([d * gl.detach(), d * val * dgelu], dim=2).reshape(M, N8))
 
 
-def conv3x3(x, w_krsc, out, *, stride=1, upsample2x=False, bias=None, rowbias=None, res1=None, split_k=0, workspace=None,
-            x_padded=False, tile=None):
-    xi = (x[:, 1:-1, 1:-1] if x_padded else x).float().permute(0, 3, 1, 2)
-    if upsample2x:
-        xi = F.interpolate(xi, scale_factor=2.0, mode="nearest")
-    w = w_krsc.float().permute(0, 3, 1, 2)                   # [Cout, 3, 3, Cin] -> [Cout, Cin, 3, 3]
-    y = F.conv2d(xi, w, None if bias is None else bias.float(), stride=stride, padding=1)
-    if rowbias is not None:
-        y = y + rowbias.float()[:, :, None, None]
-    y = y.permute(0, 2, 3, 1)
-    if res1 is not None:
-        y = y + res1.float()
-    return _store(out, y)
-
-
-def conv_in(x_nchw, w_kn, bias, out):
-    cin, cout = x_nchw.shape[1], w_kn.shape[1]
-    w = w_kn.float().reshape(3, 3, cin, cout).permute(3, 2, 0, 1)     # k = (ky*3 + kx)*Cin + ci
-    return _store(out, F.conv2d(x_nchw.float(), w, bias.float(), padding=1).permute(0, 2, 3, 1))
-
-
-def conv_out(x, w_krsc, bias, out_nchw):
-    w = w_krsc.float().permute(0, 3, 1, 2)
-    return _store(out_nchw, F.conv2d(x.float().permute(0, 3, 1, 2), w, bias.float(), padding=1))
-
-
-def pad_cast(x, out_padded):
-    out_padded[:, 1:-1, 1:-1] = x.to(out_padded.dtype)
-    return out_padded
-
-
 def zero_stuff(dy, out_padded):
     inner = out_padded[:, 1:-1, 1:-1]
     inner.zero_()
@@ -210,10 +140,6 @@ def transpose(src, dst):
 
 def transpose_batched(src, dst):
     return _store(dst, src.transpose(1, 2))
-
-
-def copy_rows(dst, src):
-    return _store(dst, src)
 
 
 def timestep_embed(t, freqs, out, flip_sin_to_cos):

@@ -15,34 +15,53 @@ def _store(out: torch.Tensor, val: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def gemm(a, w, out, *, bias=None, rowbias=None, rows_per_batch=1, res1=None, res2=None, epilogue=0, split_k=0, workspace=None, out2=None,
-         tile=None, use_table=True, stats=None):
-    assert epilogue == 0 and rowbias is None and stats is None
+EPI_LINEAR, EPI_GEGLU = 0, 1
+
+
+def gemm(a, w, out, *, bias=None, rowbias=None, rows_per_batch=1, res1=None, res2=None, epilogue=EPI_LINEAR, split_k=0, workspace=None,
+         out2=None, tile=None, use_table=True, stats=None):
+    """The one stand-in of ops.gemm (tests/fake_ops.py imports it): fp32 accumulation, one rounding to the dtype of `out`.  split_k,
+    workspace, tile and use_table only choose a launch; stats (the GroupNorm partials of the output) is not emulated and refused."""
+    assert stats is None, "gemm stand-in: stats= is not emulated"
     assert a.dtype == torch.float16 and w.dtype == torch.float16 and a.shape[1] == w.shape[1]
     assert a.shape[1] % 8 == 0 and w.shape[0] % 8 == 0, "sg_gemm_f16: K and N must be multiples of 8"
+    M, N = a.shape[0], w.shape[0]
     v = a.float() @ w.float().t()
     if bias is not None:
         v = v + bias.float()[None]
-    if res1 is not None:
-        v = v + res1.float()
-    if res2 is not None:
-        v = v + res2.float()
+    if rowbias is not None:                  # row m takes rowbias[m // rows_per_batch, :N]
+        v = v + rowbias.float()[torch.arange(M) // rows_per_batch, :N]
+    if epilogue == EPI_GEGLU:                # columns come in blocks of 64: 32 values then their 32 gates -> val * gelu(gate)
+        assert N % 64 == 0 and res1 is None and res2 is None, "sg_gemm_f16: GEGLU needs N % 64 == 0 and takes no residual"
+        v = v.view(M, N // 64, 2, 32)
+        v = (v[:, :, 0] * F.gelu(v[:, :, 1])).reshape(M, N // 2)
+    else:
+        if res1 is not None:
+            v = v + res1.float()
+        if res2 is not None:
+            v = v + res2.float()
     assert tuple(out.shape) == tuple(v.shape)
+    if out2 is not None:
+        _store(out2, v)
     return _store(out, v)
 
 
 def conv3x3(x, w_krsc, out, *, stride=1, upsample2x=False, bias=None, rowbias=None, res1=None, split_k=0, workspace=None, x_padded=False,
             tile=None, stats=None):
-    assert x.dtype == torch.float16 and w_krsc.dtype == torch.float16 and rowbias is None and stats is None
-    assert x.shape[3] % 64 == 0 and w_krsc.shape[0] % 8 == 0
+    """The one stand-in of ops.conv3x3.  With x_padded the kernel addresses padded pixel (oy*stride + ky, ox*stride + kx) of the tensor it
+    is HANDED, whatever its border holds: the zero-bordered image of the UNet and the view shifted by one row and one pixel of
+    VaeEngine.encode are the same call.  stats and defer_reduce are not emulated.  The kernel wants Cin % 64 == 0; the stand-in takes any
+    multiple of 8, because the training-composition tests run the host logic at 32 channels."""
+    assert stats is None, "conv3x3 stand-in: stats= is not emulated"
+    assert x.dtype == torch.float16 and w_krsc.dtype == torch.float16
+    assert x.shape[3] % 8 == 0 and w_krsc.shape[0] % 8 == 0, "sg_conv3x3: Cin and Cout must be multiples of 8"
     B, Ho, Wo, Co = out.shape
     wt = w_krsc.float().permute(0, 3, 1, 2)                       # [Co, Ci, 3, 3]
     xf = x.float().permute(0, 3, 1, 2)                            # [B, Ci, H(+2), W(+2)]
     if upsample2x:
-        assert x_padded and stride == 1
-        v = F.conv2d(F.interpolate(xf[:, :, 1:-1, 1:-1], scale_factor=2.0, mode="nearest"), wt, padding=1)
+        assert stride == 1
+        v = F.conv2d(F.interpolate(xf[:, :, 1:-1, 1:-1] if x_padded else xf, scale_factor=2.0, mode="nearest"), wt, padding=1)
     elif x_padded:
-        # the kernel addresses padded pixel (oy*stride + ky, ox*stride + kx) of the tensor it is handed
         need_h, need_w = (Ho - 1) * stride + 3, (Wo - 1) * stride + 3
         assert need_h <= xf.shape[2] and need_w <= xf.shape[3]
         v = F.conv2d(xf[:, :, :need_h, :need_w], wt, stride=stride, padding=0)
@@ -51,6 +70,8 @@ def conv3x3(x, w_krsc, out, *, stride=1, upsample2x=False, bias=None, rowbias=No
     v = v.permute(0, 2, 3, 1)
     if bias is not None:
         v = v + bias.float()
+    if rowbias is not None:                  # one row per image: rowbias[b, :Cout]
+        v = v + rowbias.float()[:, None, None, :Co]
     if res1 is not None:
         v = v + res1.float()
     assert tuple(v.shape) == tuple(out.shape), (v.shape, out.shape)
@@ -61,7 +82,7 @@ def conv_in(x_nchw, w_kn, bias, out):
     B, Ci, H, W = x_nchw.shape
     Co = w_kn.shape[1]
     assert Ci <= 8 and Co % 8 == 0 and tuple(w_kn.shape) == (9 * Ci, Co)
-    wt = w_kn.float().view(3, 3, Ci, Co).permute(3, 2, 0, 1)
+    wt = w_kn.float().view(3, 3, Ci, Co).permute(3, 2, 0, 1)          # k = (ky*3 + kx)*Cin + ci
     v = F.conv2d(x_nchw.float(), wt, bias.float(), padding=1).permute(0, 2, 3, 1)
     return _store(out, v)
 
@@ -74,6 +95,9 @@ def conv_out(x, w_krsc, bias, out_nchw):
 
 
 def groupnorm(x, gamma, beta, out, groups, eps, silu, workspace, xcopy=None, pstats=None):
+    """The one stand-in of ops.groupnorm.  pstats (statistics from the producers' epilogues) cannot exist here, because the gemm and
+    conv3x3 stand-ins refuse stats=; split= is not emulated."""
+    assert not pstats, "groupnorm stand-in: pstats= is not emulated"
     B, HW, Cc = x.shape
     v = F.group_norm(x.float().transpose(1, 2), groups, gamma.float(), beta.float(), eps).transpose(1, 2)
     if silu:
@@ -88,7 +112,10 @@ def groupnorm(x, gamma, beta, out, groups, eps, silu, workspace, xcopy=None, pst
 
 
 def layernorm(x, g1, b1, y1, eps=1e-5, g2=None, b2=None, y2=None):
-    _store(y1, F.layer_norm(x.float(), (x.shape[1],), g1.float(), b1.float(), eps))
+    C = x.shape[-1]
+    _store(y1, F.layer_norm(x.float(), (C,), g1.float(), b1.float(), eps))
+    if y2 is not None:                       # the second affine output from the same statistics
+        _store(y2, F.layer_norm(x.float(), (C,), g2.float(), b2.float(), eps))
 
 
 def pad_cast(x, out_padded):
