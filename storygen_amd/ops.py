@@ -385,6 +385,17 @@ def gemm_pair(first: tuple, second: tuple) -> None:
         check(lib.sg_gemm_pair_f16(C.byref(d0), C.byref(d1), _stream()), "sg_gemm_pair_f16")
 
 
+def gemm_pair_launch_plan(first: tuple, second: tuple) -> tuple:
+    """What a gemm_pair() call with these arguments will launch (sg_gemm_pair_launch_plan; no launch): (1 if one launch serves both problems,
+    the six integers of gemm_launch_plan for problem 0, for problem 1, workgroups of the shared launch or 0)."""
+    (a0, kw0), (a1, kw1) = first, second
+    d0, _, _ = _gemm_desc(*a0, use_table=False, **kw0)
+    d1, _, _ = _gemm_desc(*a1, use_table=False, **kw1)
+    out = (C.c_int32 * 14)()
+    check(lib.sg_gemm_pair_launch_plan(C.byref(d0), C.byref(d1), out), "sg_gemm_pair_launch_plan")
+    return tuple(out)
+
+
 def _conv_desc(x: torch.Tensor, w_krsc: torch.Tensor, out: torch.Tensor, *, stride: int = 1, upsample2x: bool = False,
                bias: Optional[torch.Tensor] = None, rowbias: Optional[torch.Tensor] = None,
                res1: Optional[torch.Tensor] = None, split_k: int = 0, workspace: Optional[torch.Tensor] = None,
