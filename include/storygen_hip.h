@@ -731,6 +731,66 @@ int sg_adjacent_cosine_f64(const float* feats, int64_t ldf, int32_t N, int32_t d
                            uint8_t* drop, sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Human and text masks from a detector's output (data_process/yolov7/human_ocr_mask.py:34-70; utils/general.py non_max_suppression,
+ * scale_coords, clip_coords): everything between `pred = model(img)[0]` and the bytes of the mask, on the device, exact.  All
+ * arithmetic is fp32 with one rounding per operation (no fused multiply-add, no reciprocal); fp16 input is converted on load.  That
+ * is the script's CPU path; its CUDA path computes in fp16 and is not reproduced.
+ *
+ * sg_det_select: pred [B, A, 5 + nc] (fp32, or fp16 with pred_f16 = 1; batch / row strides bsp / ldp in elements), a row being
+ *   (x, y, w, h, obj, cls_0 .. cls_{nc-1}) -> cand fp32 [B, max_nms, 6] = (x1, y1, x2, y2, conf, cls), ncand int32 [B].  Per anchor, in order:
+ *     1. obj > conf_thres;
+ *     2. conf_c = cls_c * obj (one multiply per class); nc == 1: conf = obj, class 0;
+ *     3. the best class is the FIRST maximum (torch.max on the CPU); conf > conf_thres; a NaN among the conf_c drops the anchor
+ *        (torch.max hands it on and it fails the comparison), as a NaN obj does;
+ *     4. the best class is one of `classes` (a HOST list of n_classes ids; n_classes = 0: every class; an id >= nc matches nothing);
+ *     5. box = (x - w / 2, y - h / 2, x + w / 2, y + h / 2).
+ *   Survivors are taken in anchor order, then ordered by conf descending with equal scores in anchor order (the script's argsort and
+ *   torchvision's sort are not stable; this order is defined here), and the first max_nms of them are written: ncand[b] =
+ *   min(survivors, max_nms); rows of cand at and beyond ncand[b] are left untouched.
+ *   Two launches: one workgroup per image appends the survivors to the workspace in anchor order (ballot + per-wave totals, no atomics);
+ *   then a counting rank (O(n^2) comparisons over the n survivors) places each.  workspace: sg_det_select_workspace_bytes(B, A) bytes,
+ *   4-byte aligned, the caller's (0 is returned for sizes outside the limits).
+ *
+ * sg_det_nms: greedy NMS as torchvision.ops.nms defines it, on the boxes the script hands it, then scale_coords and .round().
+ *   Candidate j is suppressed by an earlier kept candidate i when inter / ((area_i + area_j) - inter) > iou_thres, with
+ *   inter = max(0, min(x2) - max(x1)) * max(0, min(y2) - max(y1)), area = (x2 - x1) * (y2 - y1), on the coordinates box + cls * 4096
+ *   (fp32 add; the plain box with agnostic = 1); max / min are std::max / std::min as torchvision's CPU kernel calls them.  A NaN ratio
+ *   (0 / 0 of two empty boxes) suppresses nothing.  The first max_det kept candidates are written, in score order:
+ *     det[b, k] = (rx1, ry1, rx2, ry2, conf, cls),  rx = rint(min(max((x - pad_x) / gain, 0), w0))  (y: pad_y, h0)
+ *   geom: DEVICE fp32 [B, 5] = (pad_x, pad_y, gain, w0, h0) per image — the script's Python-double gain = min(h1 / h0, w1 / w0) and
+ *   pad = ((w1 - w0 gain) / 2, (h1 - h0 gain) / 2) rounded to fp32, which is what torch's in-place `-=` and `/=` with a Python scalar
+ *   compute with; the division is a true fp32 division and the rounding is half to even.  A NaN coordinate ends as 0 (defined here:
+ *   the script raises on int(nan)).  count[b] = rows written; rows at and beyond it are left untouched.
+ *   One workgroup per image: a bitmap of removed candidates in LDS, a uniform walk to the next candidate still in, one sweep of the later
+ *   candidates per kept one (a wave owns whole 64-bit words: no LDS atomics), at most max_det sweeps.
+ *
+ * sg_box_mask_u8: one frame's mask, uint8 [h0, w0, 3] (row stride ldm in bytes), every byte 0 or 255 (cv2.imwrite's cast of mask * 255).
+ *   Rectangles: rows [0, min(*count, max_det)) of det (fp32 [max_det, 6] on the device, int() of the four coordinates; NULL with
+ *   count NULL and max_det 0 for none) and n_text int32 (x1, y1, x2, y2) rectangles (device).  A rectangle covers mask[y1:y2, x1:x2]
+ *   as NumPy slices: a negative end wraps once by the size, both ends are clamped to [0, size], empty where start >= stop.
+ *   *covered (int32, device) = number of pixels under the det rectangles alone (their union): the script takes its ratio before it
+ *   adds the text boxes.  Every byte of the h0 x 3 w0 window is written exactly once, 16 bytes per store where mask is 16-byte
+ *   aligned and ldm % 16 == 0; nothing else is written.  *covered is cleared by a memset node on the stream, then one integer atomic
+ *   per row adds to it.
+ * SG_EINVAL before any launch: null pointers, sizes outside the limits below, strides below the extent, NaN thresholds, a negative
+ * class id, a workspace too small or misaligned, outputs that overlap each other. */
+#define SG_DET_MAX_BATCH 4096
+#define SG_DET_MAX_ANCHORS 1048576
+#define SG_DET_MAX_NC 1024
+#define SG_DET_MAX_NMS 30000
+#define SG_DET_MAX_DET 1024
+#define SG_MASK_MAX_SIDE 16384
+#define SG_MASK_MAX_TEXT 1024
+size_t sg_det_select_workspace_bytes(int32_t B, int32_t A);
+int sg_det_select(const void* pred, int32_t pred_f16, int64_t bsp, int64_t ldp, int32_t B, int32_t A, int32_t nc, float conf_thres,
+                  const int32_t* classes, int32_t n_classes, int32_t max_nms, float* cand, int32_t* ncand, void* workspace,
+                  size_t workspace_bytes, sg_stream_t stream);
+int sg_det_nms(const float* cand, const int32_t* ncand, int32_t B, int32_t max_nms, float iou_thres, int32_t agnostic, int32_t max_det,
+               const float* geom, float* det, int32_t* count, sg_stream_t stream);
+int sg_box_mask_u8(uint8_t* mask, int64_t ldm, int32_t h0, int32_t w0, const float* det, const int32_t* count, int32_t max_det,
+                   const int32_t* text, int32_t n_text, int32_t* covered, sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimizer step of the training loop: /root/reference/train_StorySalon_stage2.py:186-205 builds torch.optim.AdamW
  * or bitsandbytes' AdamW8bit over the trainable (attn3) parameters, :328-333 clips the global gradient norm and steps.
  *

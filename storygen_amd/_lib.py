@@ -253,6 +253,13 @@ SIGNATURES = {
                                   C.c_void_p]),
     "sg_adjacent_cosine_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "sg_det_select_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "sg_det_select": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_int32),
+                                C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sg_det_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p]),
+    "sg_box_mask_u8": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                 C.c_void_p]),
     "sg_sumsq_scratch_floats": (C.c_size_t, []),
     "sg_sumsq_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sg_adamw_f32": (C.c_int, [C.POINTER(AdamWDesc), C.c_void_p]),

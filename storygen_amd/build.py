@@ -22,7 +22,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libstorygen_hip.so")
 LIB_EXP = os.path.join(LIBDIR, "libstorygen_hip_exp.so")      # --experiments: a SEPARATE library that only tools/anatomy.py loads
-SOURCES = ["gemm_conv.hip", "attention.hip", "attention_f8.hip", "norm.hip", "misc.hip", "backward.hip", "attention_bwd.hip", "encoders.hip", "optim.hip", "ff_fused.hip", "attention_enc.hip", "story.hip", "image.hip", "clip_u8.hip", "align.hip", "dedup.hip"]
+SOURCES = ["gemm_conv.hip", "attention.hip", "attention_f8.hip", "norm.hip", "misc.hip", "backward.hip", "attention_bwd.hip", "encoders.hip", "optim.hip", "ff_fused.hip", "attention_enc.hip", "story.hip", "image.hip", "clip_u8.hip", "align.hip", "dedup.hip", "mask.hip"]
 # -fno-slp-vectorize for EVERY kernel (round 6): no packed fp32 VALU (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32 with op_sel).
 #  * correctness: the one run-to-run difference this project ever saw — the columns-are-tokens LayerNorm fold on the 4-stage latency
 #    kernel under the two-branch graph — was ONE half of a `v_pk_add_f32 ..., v[c:d] op_sel:[0,1]` in the epilogue losing its d term
@@ -47,7 +47,10 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "attenti
                "attention_enc.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # the GELU polynomial of the fused feed-forward runs beside MFMAs: packed fp32 VALU (what SLP vectorisation makes of it)
                # is slower there than the scalar forms (MI355X_MICROARCH.md, price of fillers beside MFMAs)
-               "ff_fused.hip": []}
+               "ff_fused.hip": [],
+               # detections and masks are exact: an FMA fused into an IoU or a rescale changes a decision (the file spells the operations
+               # with __f*_rn as well)
+               "mask.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

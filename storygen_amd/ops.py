@@ -1311,6 +1311,161 @@ def adjacent_cosine(feats: torch.Tensor, threshold: float = 0.75, eps: float = 1
     return sim, drop
 
 
+# SG_DET_* / SG_MASK_*: limits of sg_det_select / sg_det_nms / sg_box_mask_u8 (include/storygen_hip.h)
+DET_MAX_BATCH, DET_MAX_ANCHORS, DET_MAX_NC, DET_MAX_NMS, DET_MAX_DET = 4096, 1 << 20, 1024, 30000, 1024
+MASK_MAX_SIDE, MASK_MAX_TEXT = 16384, 1024
+
+
+def _i32(t: torch.Tensor, name: str):
+    if t.dtype != torch.int32 or not t.is_cuda:
+        raise TypeError(f"{name}: expected a CUDA/HIP int32 tensor, got {t.dtype} on {t.device}")
+
+
+def _given(who: str, t: Optional[torch.Tensor], name: str, dtype, shape, device) -> torch.Tensor:
+    """An output of a detection op: allocated when not given, else a contiguous tensor of that type and shape (a window of a larger
+    buffer is fine)."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if t.dtype != dtype or not t.is_cuda:
+        raise TypeError(f"{name}: expected a CUDA/HIP {dtype} tensor, got {t.dtype} on {t.device}")
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def check_det_sides(who: str, B: int, A: int, nc: int, max_nms: int, max_det: int) -> None:
+    if B < 1 or B > DET_MAX_BATCH:
+        raise ValueError(f"{who}: {B} images are outside [1, {DET_MAX_BATCH}]")
+    if A < 1 or A > DET_MAX_ANCHORS:
+        raise ValueError(f"{who}: {A} anchors are outside [1, {DET_MAX_ANCHORS}]")
+    if nc < 1 or nc > DET_MAX_NC:
+        raise ValueError(f"{who}: {nc} classes are outside [1, {DET_MAX_NC}]")
+    if max_nms < 1 or max_nms > DET_MAX_NMS:
+        raise ValueError(f"{who}: max_nms = {max_nms} is outside [1, {DET_MAX_NMS}]")
+    if max_det < 1 or max_det > DET_MAX_DET:
+        raise ValueError(f"{who}: max_det = {max_det} is outside [1, {DET_MAX_DET}]")
+
+
+def check_mask_frame(who: str, h0: int, w0: int) -> None:
+    if h0 < 1 or w0 < 1 or h0 > MASK_MAX_SIDE or w0 > MASK_MAX_SIDE:
+        raise ValueError(f"{who}: a {h0} x {w0} frame is outside [1, {MASK_MAX_SIDE}] per side")
+
+
+def det_select_workspace_bytes(B: int, A: int) -> int:
+    return lib.sg_det_select_workspace_bytes(B, A)
+
+
+def det_select(pred: torch.Tensor, conf_thres: float = 0.5, classes: tuple = (), max_nms: int = 30000, cand: Optional[torch.Tensor] = None,
+               ncand: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> tuple:
+    """pred fp32 or fp16 [B, A, 5 + nc] (any batch / row stride), rows (x, y, w, h, obj, cls ...) -> (cand fp32 [B, max_nms, 6], ncand int32
+    [B]) on the device: per image the anchors with obj > conf_thres, conf = max_c cls_c * obj > conf_thres (first maximum; conf = obj at
+    nc == 1) and the best class in `classes` (empty: all), as (x1, y1, x2, y2, conf, cls), ordered by conf descending with equal scores in
+    anchor order, the first max_nms of them; ncand[b] rows are written (sg_det_select: non_max_suppression's filter, utils/general.py:
+    617-679, in fp32).  workspace: uint8 of det_select_workspace_bytes(B, A), allocated when not given."""
+    _act(pred, "pred")
+    if pred.dim() != 3 or pred.shape[2] < 6:
+        raise ValueError(f"det_select: pred must be [B, A, 5 + nc] with nc >= 1, got {tuple(pred.shape)}")
+    B, A, nc = pred.shape[0], pred.shape[1], pred.shape[2] - 5
+    max_nms = int(max_nms)
+    check_det_sides("det_select", B, A, nc, max_nms, 1)
+    conf_thres = float(conf_thres)
+    if conf_thres != conf_thres:
+        raise ValueError("det_select: conf_thres is NaN")
+    classes = tuple(int(c) for c in classes)
+    if any(c < 0 for c in classes) or len(classes) > DET_MAX_NC:
+        raise ValueError(f"det_select: classes {classes} hold a negative id or more than {DET_MAX_NC} ids")
+    if pred.stride(2) != 1:
+        raise ValueError("det_select: innermost dimension must be contiguous")
+    ldp = max(pred.stride(1), 5 + nc) if A == 1 else pred.stride(1)       # (the stride of a single row / image is never used)
+    bsp = max(pred.stride(0), A * ldp) if B == 1 else pred.stride(0)
+    if ldp < 5 + nc or bsp < A * ldp:
+        raise ValueError(f"det_select: pred overlaps itself (row stride {ldp}, batch stride {bsp} for {A} rows of {5 + nc})")
+    dev = pred.device
+    cand = _given("det_select", cand, "cand", torch.float32, (B, max_nms, 6), dev)
+    ncand = _given("det_select", ncand, "ncand", torch.int32, (B,), dev)
+    need = det_select_workspace_bytes(B, A)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if workspace.dtype != torch.uint8 or not workspace.is_cuda:
+        raise TypeError(f"workspace: expected a CUDA/HIP uint8 tensor, got {workspace.dtype} on {workspace.device}")
+    if workspace.dim() != 1 or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 4:
+        raise ValueError(f"det_select: workspace must be contiguous, 4-byte aligned and hold {need} bytes, got {tuple(workspace.shape)}")
+    _same_device("det_select", pred, cand=cand, ncand=ncand, workspace=workspace)
+    cl = (C.c_int32 * max(1, len(classes)))(*classes)
+    check(lib.sg_det_select(pred.data_ptr(), int(pred.dtype == torch.float16), bsp, ldp, B, A, nc, conf_thres, cl, len(classes), max_nms,
+                            cand.data_ptr(), ncand.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream()), "sg_det_select")
+    return cand, ncand
+
+
+def det_nms(cand: torch.Tensor, ncand: torch.Tensor, geom: torch.Tensor, iou_thres: float = 0.6, agnostic: bool = False, max_det: int = 300,
+            det: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None) -> tuple:
+    """cand fp32 [B, max_nms, 6] and ncand int32 [B] as det_select leaves them, geom fp32 [B, 5] = (pad_x, pad_y, gain, w0, h0) per image
+    -> (det fp32 [B, max_det, 6], count int32 [B]) on the device: greedy NMS by torchvision.ops.nms's definition on box + cls * 4096 (the
+    plain box with agnostic), the first max_det kept rows in score order with their boxes taken to the frame as scale_coords and .round()
+    do it: rint(clamp((v - pad) / gain, 0, size)) (sg_det_nms).  count[b] rows are written."""
+    _f32(cand, "cand"), _i32(ncand, "ncand"), _f32(geom, "geom")
+    if cand.dim() != 3 or cand.shape[2] != 6 or not cand.is_contiguous():
+        raise ValueError(f"det_nms: cand must be contiguous [B, max_nms, 6], got {tuple(cand.shape)}")
+    B, max_nms, max_det = cand.shape[0], cand.shape[1], int(max_det)
+    check_det_sides("det_nms", B, 1, 1, max_nms, max_det)
+    iou_thres = float(iou_thres)
+    if iou_thres != iou_thres:
+        raise ValueError("det_nms: iou_thres is NaN")
+    if tuple(ncand.shape) != (B,) or not ncand.is_contiguous():
+        raise ValueError(f"det_nms: ncand must be contiguous [{B}], got {tuple(ncand.shape)}")
+    if tuple(geom.shape) != (B, 5) or not geom.is_contiguous():
+        raise ValueError(f"det_nms: geom must be contiguous [{B}, 5], got {tuple(geom.shape)}")
+    det = _given("det_nms", det, "det", torch.float32, (B, max_det, 6), cand.device)
+    count = _given("det_nms", count, "count", torch.int32, (B,), cand.device)
+    _same_device("det_nms", cand, ncand=ncand, geom=geom, det=det, count=count)
+    check(lib.sg_det_nms(cand.data_ptr(), ncand.data_ptr(), B, max_nms, iou_thres, int(bool(agnostic)), max_det, geom.data_ptr(), det.data_ptr(),
+                         count.data_ptr(), _stream()), "sg_det_nms")
+    return det, count
+
+
+def box_mask(h0: int, w0: int, det: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None, text: Optional[torch.Tensor] = None,
+             out: Optional[torch.Tensor] = None, covered: Optional[torch.Tensor] = None) -> tuple:
+    """-> (mask uint8 [h0, w0, 3] of 0 / 255, covered int32 [1]) on the device: mask[y1:y2, x1:x2] = 255 with NumPy's slice rules for the first
+    count[0] rows of det (fp32 [max_det, 6], one image of det_nms's output; int() of its coordinates) and for every row of text (int32
+    [T, 4], x1 y1 x2 y2); covered = the pixels under the det rectangles alone (sg_box_mask_u8; human_ocr_mask.py:41-70).  out, when given,
+    is [h0, w0, 3] with contiguous pixels and any row stride.  At least one of det / text is given, or neither for an empty mask."""
+    h0, w0 = int(h0), int(w0)
+    check_mask_frame("box_mask", h0, w0)
+    if (det is None) != (count is None):
+        raise ValueError("box_mask: det and count go together")
+    first = next((t for t in (det, text, out, covered) if t is not None), None)
+    if first is None:
+        raise ValueError("box_mask: no tensor names the device (give det, text, out or covered)")
+    max_det = 0
+    if det is not None:
+        _f32(det, "det"), _i32(count, "count")
+        if det.dim() != 2 or det.shape[1] != 6 or not det.is_contiguous() or not 1 <= det.shape[0] <= DET_MAX_DET:
+            raise ValueError(f"box_mask: det must be contiguous [max_det <= {DET_MAX_DET}, 6], got {tuple(det.shape)}")
+        if tuple(count.shape) != (1,):
+            raise ValueError(f"box_mask: count must be [1], got {tuple(count.shape)}")
+        max_det = det.shape[0]
+    n_text = 0
+    if text is not None:
+        _i32(text, "text")
+        if text.dim() != 2 or text.shape[1] != 4 or not text.is_contiguous() or text.shape[0] > MASK_MAX_TEXT:
+            raise ValueError(f"box_mask: text must be contiguous [T <= {MASK_MAX_TEXT}, 4], got {tuple(text.shape)}")
+        n_text = text.shape[0]
+    dev = first.device
+    if out is None:
+        out = torch.empty(h0, w0, 3, dtype=torch.uint8, device=dev)
+    if out.dtype != torch.uint8 or not out.is_cuda:
+        raise TypeError(f"out: expected a CUDA/HIP uint8 tensor, got {out.dtype} on {out.device}")
+    if tuple(out.shape) != (h0, w0, 3) or out.stride(2) != 1 or out.stride(1) != 3 or (h0 > 1 and out.stride(0) < 3 * w0):
+        raise ValueError(f"box_mask: out must be [{h0}, {w0}, 3] with contiguous pixels and rows that do not overlap, got {tuple(out.shape)} "
+                         f"with strides {tuple(out.stride())}")
+    covered = _given("box_mask", covered, "covered", torch.int32, (1,), dev)
+    _same_device("box_mask", first, det=det, count=count, text=text, out=out, covered=covered)
+    ldm = max(out.stride(0), 3 * w0) if h0 == 1 else out.stride(0)
+    check(lib.sg_box_mask_u8(out.data_ptr(), ldm, h0, w0, _p(det), _p(count), max_det, _p(text) if n_text else None, n_text, covered.data_ptr(),
+                             _stream()), "sg_box_mask_u8")
+    return out, covered
+
+
 # ------------------------------------------------------------------------------------------------ backward pass (config 4)
 # Validated on MI355X in round 2 (tests/test_backward_gpu.py).  Kernels: csrc/backward.hip, attention_bwd.hip; formulas: oracle/storygen_backward.py.
 def layernorm_bwd(x: torch.Tensor, dy1: torch.Tensor, g1: torch.Tensor, out: torch.Tensor, eps: float = 1e-5,
