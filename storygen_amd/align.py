@@ -23,8 +23,8 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .clip_score import _sub
-from .encoders import ClipTextEngine, ClipVisionEngine, is_uint8_images
+from .clip_score import build_clip_towers
+from .encoders import is_uint8_images
 from .pick_score import check_pick_config, split_config
 
 SD = Dict[str, torch.Tensor]
@@ -95,22 +95,11 @@ class FrameAligner:
         """One CLIPModel state dict in transformers naming (vision_model.*, visual_projection.weight, text_model.*, text_projection.weight)
         and its CLIPConfig (or a dict with vision_config and text_config): ViT-B/16, or anything else within check_clip_dims_wide for the
         image tower and sg_attn_small_f16 for the text tower; quick_gelu or gelu per tower from the config."""
-        sd = clip_model_state_dict
         vc, tc = split_config(clip_config, "FrameAligner")
         check_pick_config(vc, tc, "FrameAligner")
-        if not any(k.startswith("text_model.") for k in sd) or "text_projection.weight" not in sd:
-            raise KeyError("FrameAligner: the state dict has no text tower (text_model.* and text_projection.weight, CLIPModel naming)")
-        if not any(k.startswith("vision_model.") for k in sd) or "visual_projection.weight" not in sd:
-            raise KeyError("FrameAligner: the state dict has no image tower (vision_model.* and visual_projection.weight, CLIPModel naming)")
         self.dev = torch.device(device)
         self.crop = "torchvision"                  # the `clip` package's CenterCrop, as align.py:114 preprocesses
-        self.vision = ClipVisionEngine(_sub(sd, ("vision_model.", "visual_projection.")), self.dev, heads=int(vc["num_attention_heads"]),
-                                       eps=float(vc.get("layer_norm_eps", 1e-5)), hidden_act=vc.get("hidden_act", "quick_gelu"),
-                                       image_size=int(vc["image_size"]), wide=True)
-        self.text = ClipTextEngine(_sub(sd, ("text_model.", "text_projection.")), self.dev, heads=int(tc["num_attention_heads"]),
-                                   eps=float(tc.get("layer_norm_eps", 1e-5)), hidden_act=tc.get("hidden_act", "quick_gelu"))
-        if self.text.proj.shape[0] != self.vision.pdim:
-            raise ValueError(f"FrameAligner: text projection {self.text.proj.shape[0]} and image projection {self.vision.pdim} differ")
+        self.vision, self.text = build_clip_towers(clip_model_state_dict, vc, tc, self.dev, True, "FrameAligner")
 
     def image_features(self, frames) -> torch.Tensor:
         """8-bit frames (a uint8 [N,h,w,3] array or tensor, a list of PIL RGB images or uint8 arrays, sizes may differ) -> fp32 [N, dim]."""

@@ -17,7 +17,7 @@ Models outside sg_attn_small_f16 (more than 128 tokens, head dim above 64: ViT-H
 storygen_amd/pick_score.py.  There is no CPU path."""
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -27,6 +27,7 @@ from .encoders import ClipTextEngine, ClipVisionEngine, check_clip_dims, is_uint
 SD = Dict[str, torch.Tensor]
 VISION_KEYS = ("hidden_size", "num_attention_heads", "image_size", "patch_size")
 TEXT_KEYS = ("hidden_size", "num_attention_heads")
+VISION_PREFIXES, TEXT_PREFIXES = ("vision_model.", "visual_projection."), ("text_model.", "text_projection.")
 
 
 def _cfg(config, keys, who: str) -> dict:
@@ -39,6 +40,31 @@ def _cfg(config, keys, who: str) -> dict:
 
 def _sub(sd: SD, prefixes) -> SD:
     return {k: v for k, v in sd.items() if k.startswith(prefixes)}
+
+
+def clip_grid_tokens(cfg, who: str, size_key: str = "image_size", patch_key: str = "patch_size") -> Tuple[int, int, int]:
+    """(image size S, patch size ps, tokens of the S / ps grid plus the class token) of a vision config; refuses a grid that does not tile."""
+    S, ps = int(cfg[size_key]), int(cfg[patch_key])
+    if S <= 0 or ps <= 0 or S % ps:
+        raise ValueError(f"{who}: {size_key} {S} is not a multiple of {patch_key} {ps}")
+    return S, ps, (S // ps) ** 2 + 1
+
+
+def build_clip_towers(sd: SD, vc: dict, tc: Optional[dict], dev, wide: bool, who: str):
+    """One state dict in CLIPModel naming and the towers' config dicts -> (ClipVisionEngine, ClipTextEngine); tc None: no text tower."""
+    for c, prefixes, name in ((tc, TEXT_PREFIXES, "text"), (vc, VISION_PREFIXES, "image")):            # both refusals before either engine is built
+        if c is not None and (not any(k.startswith(prefixes[0]) for k in sd) or prefixes[1] + "weight" not in sd):
+            raise KeyError(f"{who}: the state dict has no {name} tower ({prefixes[0]}* and {prefixes[1]}weight, CLIPModel naming)")
+
+    def engine(cls, c, prefixes, **kw):
+        return cls(_sub(sd, prefixes), dev, heads=int(c["num_attention_heads"]), eps=float(c.get("layer_norm_eps", 1e-5)),
+                   hidden_act=c.get("hidden_act", "quick_gelu"), **kw)
+
+    vision = engine(ClipVisionEngine, vc, VISION_PREFIXES, image_size=int(vc["image_size"]), wide=wide)
+    text = None if tc is None else engine(ClipTextEngine, tc, TEXT_PREFIXES)
+    if text is not None and text.proj.shape[0] != vision.pdim:
+        raise ValueError(f"{who}: text projection {text.proj.shape[0]} and image projection {vision.pdim} differ")
+    return vision, text
 
 
 def as_nchw(images) -> torch.Tensor:
@@ -62,28 +88,18 @@ class ClipScorer:
             raise ValueError(f"ClipScorer: crop must be one of {ops.CLIP_CROPS}, got {crop!r}")
         self.crop = crop
         vc = _cfg(vision_config, VISION_KEYS, "ClipScorer(vision_config)")
-        S, ps = int(vc["image_size"]), int(vc["patch_size"])
-        if S <= 0 or ps <= 0 or S % ps:
-            raise ValueError(f"ClipScorer: image_size {S} is not a multiple of patch_size {ps}")
-        check_clip_dims("ClipScorer (image tower)", int(vc["hidden_size"]), int(vc["num_attention_heads"]), (S // ps) ** 2 + 1)
-        tc = None
+        check_clip_dims("ClipScorer (image tower)", int(vc["hidden_size"]), int(vc["num_attention_heads"]), clip_grid_tokens(vc, "ClipScorer")[2])
+        tc, sd = None, _sub(vision_state_dict, VISION_PREFIXES)
         if text_state_dict is not None:
             if text_config is None:
                 raise ValueError("ClipScorer: text_state_dict needs text_config")
             tc = _cfg(text_config, TEXT_KEYS, "ClipScorer(text_config)")
             check_clip_dims("ClipScorer (text tower)", int(tc["hidden_size"]), int(tc["num_attention_heads"]),
                             int(tc.get("max_position_embeddings", 77)))
-            if "text_projection.weight" not in text_state_dict:
-                raise KeyError("ClipScorer: text_state_dict has no text_projection.weight (CLIPTextModelWithProjection / CLIPModel naming)")
+            sd.update(_sub(text_state_dict, TEXT_PREFIXES))
         self.dev = torch.device(device)
         self.in_scale, self.in_shift = float(in_scale), float(in_shift)
-        self.vision = ClipVisionEngine(_sub(vision_state_dict, ("vision_model.", "visual_projection.")), self.dev,
-                                       heads=int(vc["num_attention_heads"]), eps=float(vc.get("layer_norm_eps", 1e-5)),
-                                       hidden_act=vc.get("hidden_act", "quick_gelu"), image_size=S)
-        self.text = None
-        if tc is not None:
-            self.text = ClipTextEngine(_sub(text_state_dict, ("text_model.", "text_projection.")), self.dev, heads=int(tc["num_attention_heads"]),
-                                       eps=float(tc.get("layer_norm_eps", 1e-5)), hidden_act=tc.get("hidden_act", "quick_gelu"))
+        self.vision, self.text = build_clip_towers(sd, vc, tc, self.dev, False, "ClipScorer")
 
     def image_features(self, images) -> torch.Tensor:
         """Projected image embeddings, fp32 [N, projection_dim] on the device (not normalised).  images: float frames ([N,H,W,3] array in

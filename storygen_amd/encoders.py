@@ -2,9 +2,11 @@
 
   ClipTextEngine   CLIPTextModel.forward        /root/reference/model/pipeline.py:137,183; train_StorySalon_stage2.py:283-302
   VaeEngine        AutoencoderKL.encode/decode  /root/reference/model/pipeline.py:198-205,392,401; train_StorySalon_stage2.py:281-288
-  ClipVisionEngine CLIPVisionModelWithProjection over float images: the image tower of CLIP-I / CLIP-T scoring (clip_score.py)
+  ClipVisionEngine CLIPVisionModelWithProjection over float images or 8-bit frames: the image tower of CLIP-I / CLIP-T scoring
+                   (clip_score.py), PickScore and alignment; the tower itself, the layer stack both CLIP towers run and the host-side
+                   limits live in vit.py and are re-exported here
 
-Both are eager launch sequences over the UNet's kernels (sg_gemm_f16, sg_conv3x3_nhwc_f16, sg_groupnorm_nhwc_f16, sg_layernorm_f16,
+All are eager launch sequences over the UNet's kernels (sg_gemm_f16, sg_conv3x3_nhwc_f16, sg_groupnorm_nhwc_f16, sg_layernorm_f16,
 sg_conv_in/out_f16, sg_pad_cast_f16) plus the small kernels of csrc/encoders.hip; they run once per call of the pipeline, not per
 denoising step, so they are not captured into graphs.  Activations are channels-last; the residual stream is fp32, every MFMA operand
 fp16 — the UNet engine's conventions.  Parity: tests/test_encoders_gpu.py against oracle/encoders_oracle.py (CLIP pinned to
@@ -22,18 +24,10 @@ from __future__ import annotations
 import math
 from typing import Dict, Optional, Tuple
 
-import numpy as np
 import torch
 
 from . import ops, repack
-
-F16, F32 = torch.float16, torch.float32
-SD = Dict[str, torch.Tensor]
-
-
-def _count(sd: SD, prefix: str) -> int:
-    idx = {int(k[len(prefix):].split(".")[0]) for k in sd if k.startswith(prefix)}
-    return 1 + max(idx) if idx else 0
+from .vit import F16, F32, SD, VitTower, _ClipLayers, _count, check_clip_dims, check_clip_dims_wide, is_uint8_images  # noqa: F401  (re-exported)
 
 
 # ================================================================================================================== CLIP
@@ -41,87 +35,11 @@ CLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)       # the `clip` package
 CLIP_IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
-def check_clip_dims(who: str, hidden: int, heads: int, tokens: int) -> None:
-    """The limits of sg_attn_small_f16 / sg_gemm_f16 for a CLIP tower: raises ValueError before anything touches the device."""
-    if heads <= 0 or hidden % heads or hidden // heads > 64 or hidden % 8:
-        raise ValueError(f"{who}: hidden size {hidden} / {heads} heads is outside sg_attn_small_f16 (head dim <= 64)")
-    if tokens > 128:
-        raise ValueError(f"{who}: {tokens} tokens exceed sg_attn_small_f16's 128 (ViT-H/14, 257 tokens of head dim 80, is out of scope)")
-
-
-def check_clip_dims_wide(who: str, hidden: int, heads: int, tokens: int) -> None:
-    """The limits of sg_attn_enc_f16 / sg_gemm_f16 for a CLIP tower (ClipVisionEngine(wide=True): ViT-H/14, PickScore)."""
-    if heads <= 0 or hidden % heads or hidden % 8:
-        raise ValueError(f"{who}: hidden size {hidden} does not split into {heads} heads of whole 8-channel groups")
-    d = hidden // heads
-    if d % 8 or d < 8 or d > 128:
-        raise ValueError(f"{who}: head dim {d} is outside sg_attn_enc_f16 (a multiple of 8 in [8, 128])")
-    if tokens < 1 or tokens > 1024:
-        raise ValueError(f"{who}: {tokens} tokens exceed sg_attn_enc_f16's 1024")
-
-
-class _ClipLayers:
-    """The pre-LN transformer layers both CLIP towers share (transformers CLIPEncoder): weights of `encoder.layers.*` and the launch
-    sequence of one pass over them.  The residual stream is fp32, every MFMA operand fp16."""
-
-    def __init__(self, sd: SD, dev: torch.device, heads: int, eps: float, hidden_act: str, who: str):
-        if hidden_act not in ("quick_gelu", "gelu"):
-            raise ValueError(f"{who}: unsupported hidden_act {hidden_act!r}")
-        self.dev, self.heads, self.eps = dev, heads, eps
-        self.act = ops.ACT_QUICK_GELU if hidden_act == "quick_gelu" else ops.ACT_GELU
-
-        def d16(t):
-            return t.detach().to(dev, F32).to(F16).contiguous()
-
-        self.layers = []
-        for i in range(_count(sd, "encoder.layers.")):
-            p = f"encoder.layers.{i}."
-            a = p + "self_attn."
-            self.layers.append(dict(
-                ln1=(d16(sd[p + "layer_norm1.weight"]), d16(sd[p + "layer_norm1.bias"])),
-                ln2=(d16(sd[p + "layer_norm2.weight"]), d16(sd[p + "layer_norm2.bias"])),
-                wqkv=d16(torch.cat([sd[a + "q_proj.weight"], sd[a + "k_proj.weight"], sd[a + "v_proj.weight"]], 0)),
-                bqkv=d16(torch.cat([sd[a + "q_proj.bias"], sd[a + "k_proj.bias"], sd[a + "v_proj.bias"]], 0)),
-                wo=d16(sd[a + "out_proj.weight"]), bo=d16(sd[a + "out_proj.bias"]),
-                w1=d16(sd[p + "mlp.fc1.weight"]), b1=d16(sd[p + "mlp.fc1.bias"]),
-                w2=d16(sd[p + "mlp.fc2.weight"]), b2=d16(sd[p + "mlp.fc2.bias"])))
-        self.inner = self.layers[0]["w1"].shape[0]
-        self.ws = ops.new_workspace(64 << 20, dev)
-
-    def run(self, x: torch.Tensor, xo: torch.Tensor, B: int, T: int, causal: bool, key_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The first layer reads the stream x [B*T, C] (fp32, or the fp16 output of a LayerNorm), every layer leaves its result in the fp32
-        stream xo (which may be x itself).  Returns an fp16 [B*T, C] scratch buffer for the caller's final LayerNorm."""
-        M, C = xo.shape
-        H, dev = self.heads, self.dev
-        x2 = torch.empty_like(xo)
-        h16 = torch.empty(M, C, dtype=F16, device=dev)
-        qkv = torch.empty(M, 3 * C, dtype=F16, device=dev)
-        a16 = torch.empty(M, C, dtype=F16, device=dev)
-        u16 = torch.empty(M, self.inner, dtype=F16, device=dev)
-        q3 = qkv.view(B, T, 3 * C)
-        scale = (C // H) ** -0.5
-        # per tower: the scalar LDS-resident kernel where it fits (CLIP text, ViT-B/32), the MFMA encoder kernel beyond it (ViT-H/14)
-        attn = ops.attention_small if T <= 128 and C // H <= 64 else ops.attention_enc
-        for L in self.layers:
-            ops.layernorm(x, L["ln1"][0], L["ln1"][1], h16, self.eps)
-            ops.gemm(h16, L["wqkv"], qkv, bias=L["bqkv"], workspace=self.ws)
-            attn(q3[:, :, :C], q3[:, :, C:2 * C], q3[:, :, 2 * C:], a16.view(B, T, C), H, scale, causal, key_bias)
-            ops.gemm(a16, L["wo"], x2, bias=L["bo"], res1=x, workspace=self.ws)
-            ops.layernorm(x2, L["ln2"][0], L["ln2"][1], h16, self.eps)
-            ops.gemm(h16, L["w1"], u16, bias=L["b1"], workspace=self.ws)
-            ops.act_rows(u16, self.act)
-            ops.gemm(u16, L["w2"], xo, bias=L["b2"], res1=x2, workspace=self.ws)
-            x = xo
-        return h16
-
-
 class ClipTextEngine:
     """CLIP text transformer (pre-LN, causal, quick_gelu) — transformers 4.27.4 CLIPTextTransformer."""
 
     def __init__(self, state_dict: SD, device, heads: int = 12, eps: float = 1e-5, hidden_act: str = "quick_gelu"):
         sd = {k[len("text_model."):] if k.startswith("text_model.") else k: v for k, v in state_dict.items()}
-        if hidden_act not in ("quick_gelu", "gelu"):
-            raise ValueError(f"ClipTextEngine: unsupported hidden_act {hidden_act!r}")
         self.dev = torch.device(device)
         self.heads, self.eps = heads, eps
 
@@ -133,10 +51,9 @@ class ClipTextEngine:
 
         self.tok, self.pos = d32("embeddings.token_embedding.weight"), d32("embeddings.position_embedding.weight")
         self.vocab, self.C = self.tok.shape
-        if self.C % heads or self.C // heads > 64 or self.C % 8:
-            raise ValueError(f"ClipTextEngine: hidden size {self.C} / {heads} heads is outside sg_attn_small_f16 (head dim <= 64)")
+        check_clip_dims("ClipTextEngine", self.C, heads, 0)                # (the sequence length is __call__'s to refuse)
         self.stack = _ClipLayers(sd, self.dev, heads, eps, hidden_act, "ClipTextEngine")
-        self.layers, self.inner, self.ws, self.act = self.stack.layers, self.stack.inner, self.stack.ws, self.stack.act
+        self.ws = self.stack.ws
         self.lnf = (d16(sd["final_layer_norm.weight"]), d16(sd["final_layer_norm.bias"]))
         # CLIPTextModelWithProjection's head, when the checkpoint has one (CLIP-T scoring)
         self.proj = d16(sd["text_projection.weight"]) if "text_projection.weight" in sd else None
@@ -174,69 +91,25 @@ class ClipTextEngine:
         return ops.gemm(pooled.to(self.dev, F16).contiguous(), self.proj, out, workspace=self.ws)
 
 
-def is_uint8_images(images) -> bool:
-    """True for what the scorers and ClipVisionEngine treat as 8-bit frames: a uint8 array or tensor, or a list / tuple whose first entry is a
-    PIL image or a uint8 array / tensor.  Anything else (float tensors and arrays) takes the float path."""
-    if isinstance(images, (list, tuple)):
-        if len(images) == 0:
-            return False
-        first = images[0]
-        if hasattr(first, "mode") and hasattr(first, "size") and not isinstance(first, (np.ndarray, torch.Tensor)):      # a PIL image
-            return True
-        images = first
-    if isinstance(images, np.ndarray):
-        return images.dtype == np.uint8
-    return isinstance(images, torch.Tensor) and images.dtype == torch.uint8
-
-
 class ClipVisionEngine:
-    """CLIP image tower with its projection head — transformers CLIPVisionTransformer + visual_projection (ViT-B/32 class: at most 128
-    tokens, head dim <= 64), fed by sg_clip_patchify_f16: float images of any size in, (image_embeds, last_hidden_state) out.
-    wide=True lifts the limits to sg_attn_enc_f16's (up to 1024 tokens, head dim a multiple of 8 up to 128: ViT-H/14, PickScore) and
-    rounds the patch row 3 * ps^2 up to a multiple of 8 (patch size 14: 588 -> 592, zero columns appended once to the fp16 patch weight)."""
+    """CLIP image tower with its projection head — transformers CLIPVisionTransformer + visual_projection: a VitTower (vit.py) with
+    pre_layrnorm, post_layernorm and no patch bias, then the projection GEMM.  Float images of any size or 8-bit frames in,
+    (image_embeds, last_hidden_state) out.  Narrow (ViT-B/32 class: at most 128 tokens, head dim <= 64) unless wide=True (ViT-H/14,
+    PickScore; ViT-B/16, alignment)."""
 
     def __init__(self, state_dict: SD, device, heads: int = 12, eps: float = 1e-5, hidden_act: str = "quick_gelu",
                  image_size: Optional[int] = None, wide: bool = False):
+        who = "ClipVisionEngine"
         sd = {k[len("vision_model."):] if k.startswith("vision_model.") else k: v for k, v in state_dict.items()}
-        wp = sd["embeddings.patch_embedding.weight"]                       # [C, 3, ps, ps]
-        pos = sd["embeddings.position_embedding.weight"]                   # [T, C]
-        self.C, self.ps, self.T = wp.shape[0], wp.shape[2], pos.shape[0]
-        grid = math.isqrt(self.T - 1)
-        if wp.dim() != 4 or wp.shape[1] != 3 or wp.shape[3] != self.ps or grid * grid != self.T - 1 or grid == 0:
-            raise ValueError(f"ClipVisionEngine: patch weight {tuple(wp.shape)} / {self.T} positions are not a square grid of RGB patches")
-        self.S = grid * self.ps
-        if image_size is not None and image_size != self.S:
-            raise ValueError(f"ClipVisionEngine: image_size {image_size} does not match {grid} x {grid} patches of {self.ps}")
-        K = 3 * self.ps * self.ps
-        self.wide, self.kpad = bool(wide), K
-        if wide:
-            check_clip_dims_wide("ClipVisionEngine", self.C, heads, self.T)
-            if K % 4:
-                raise ValueError(f"ClipVisionEngine: 3 * patch_size^2 = {K} must be a multiple of 4")
-            self.kpad = (K + 7) & ~7
-        else:
-            check_clip_dims("ClipVisionEngine", self.C, heads, self.T)
-            if K % 8:
-                raise ValueError(f"ClipVisionEngine: 3 * patch_size^2 = {K} must be a multiple of 8")
         self.pdim = sd["visual_projection.weight"].shape[0]
         if self.pdim % 8:
-            raise ValueError(f"ClipVisionEngine: projection_dim {self.pdim} must be a multiple of 8")
-        self.dev = torch.device(device)
-        self.heads, self.eps = heads, eps
-
-        def d16(t):
-            return t.detach().to(self.dev, F32).to(F16).contiguous()
-
-        self.wp = d16(wp.reshape(self.C, K))                               # (c, dy, dx) columns: the patchify kernel's order
-        if self.kpad != K:                                                 # zero columns against the zero columns of the padded patch rows
-            self.wp = torch.nn.functional.pad(self.wp, (0, self.kpad - K)).contiguous()
-        self.cls = sd["embeddings.class_embedding"].detach().to(self.dev, F32).contiguous()
-        self.pos = pos.detach().to(self.dev, F32).contiguous()
-        self.pre = (d16(sd["pre_layrnorm.weight"]), d16(sd["pre_layrnorm.bias"]))
-        self.post = (d16(sd["post_layernorm.weight"]), d16(sd["post_layernorm.bias"]))
-        self.proj = d16(sd["visual_projection.weight"])
-        self.stack = _ClipLayers(sd, self.dev, heads, eps, hidden_act, "ClipVisionEngine")
-        self.ws = self.stack.ws
+            raise ValueError(f"{who}: projection_dim {self.pdim} must be a multiple of 8")
+        t = self.tower = VitTower(who, device, sd["embeddings.patch_embedding.weight"], sd["embeddings.position_embedding.weight"],
+                                  sd["embeddings.class_embedding"], sd, (sd["post_layernorm.weight"], sd["post_layernorm.bias"]), heads, eps,
+                                  hidden_act, wide, pre_ln=(sd["pre_layrnorm.weight"], sd["pre_layrnorm.bias"]), image_size=image_size)
+        self.C, self.ps, self.T, self.S, self.kpad, self.wide = t.C, t.ps, t.T, t.S, t.kpad, t.wide
+        self.heads, self.eps, self.wp, self.ws, self.dev = t.heads, t.eps, t.wp, t.ws, t.dev
+        self.proj = sd["visual_projection.weight"].detach().to(self.dev, F32).to(F16).contiguous()
 
     def __call__(self, images, in_scale: float = 1.0, in_shift: float = 0.0, mean=CLIP_IMAGE_MEAN, std=CLIP_IMAGE_STD,
                  crop: str = "torchvision") -> Tuple[torch.Tensor, torch.Tensor]:
@@ -246,71 +119,19 @@ class ClipVisionEngine:
         differ) are preprocessed as the reference's scripts preprocess saved images instead: Pillow's 8-bit bicubic resize bit for bit, the
         centre crop of `crop` (ops.clip_u8_geometry), ToTensor + Normalize — sg_clip_patchify_u8, one launch per size.  in_scale / in_shift do
         not apply to them; `crop` applies to them only."""
-        dev, C, T, K = self.dev, self.C, self.T, 3 * self.ps * self.ps
         if is_uint8_images(images):
-            a16 = self._patch_rows_u8(images, mean, std, crop)
-            B = a16.shape[0] // (T - 1)
-            return self._encode(a16, B)
-        if images.dim() != 4 or images.shape[1] != 3:
+            if crop not in ops.CLIP_CROPS:
+                raise ValueError(f"ClipVisionEngine: crop must be one of {ops.CLIP_CROPS}, got {crop!r}")
+            a16 = self.tower.patch_rows_u8(images, mean, std, lambda h, w: ops.clip_u8_geometry(h, w, self.S, crop))
+        elif images.dim() != 4 or images.shape[1] != 3:
             raise ValueError(f"ClipVisionEngine: expected [B,3,H,W], got {tuple(images.shape)}")
-        B = images.shape[0]
-        img = images.detach().to(dev, F32).contiguous()
-        a16 = torch.empty(B * (T - 1), self.kpad, dtype=F16, device=dev)
-        if self.kpad == K:
-            ops.clip_patchify(img, a16, self.S, self.ps, mean, std, in_scale, in_shift)
         else:
-            ops.clip_patchify(img, a16, self.S, self.ps, mean, std, in_scale, in_shift, kpad=self.kpad)
-        return self._encode(a16, B)
-
-    def _patch_rows_u8(self, images, mean, std, crop: str) -> torch.Tensor:
-        """8-bit frames -> the patch GEMM's fp16 operand [B * (T - 1), kpad]; frames of one size share a launch, as image.py groups them."""
-        from .image import _as_u8
-        if crop not in ops.CLIP_CROPS:
-            raise ValueError(f"ClipVisionEngine: crop must be one of {ops.CLIP_CROPS}, got {crop!r}")
-        if isinstance(images, np.ndarray):
-            images = torch.from_numpy(np.ascontiguousarray(images))
-        groups = {}                                          # (h, w, 3) -> [(index, uint8 [h,w,3])], or the whole [B,h,w,3] tensor
-        if isinstance(images, torch.Tensor):
-            if images.dim() != 4 or images.shape[3] != 3 or 0 in images.shape:
-                raise ValueError(f"ClipVisionEngine: uint8 frames must be [B,h,w,3], got {tuple(images.shape)}")
-            groups[tuple(images.shape[1:])] = images
-        else:
-            if len(images) == 0:
-                raise ValueError("ClipVisionEngine: no frames")
-            for i, im in enumerate(images):
-                t = _as_u8(im, 3, "ClipVisionEngine")
-                if t.shape[2] != 3:
-                    raise ValueError(f"ClipVisionEngine: frames are RGB [h,w,3], got {tuple(t.shape)}")
-                groups.setdefault(tuple(t.shape), []).append((i, t))
-        B, P = len(images), self.T - 1
-        a16 = torch.empty(B * P, self.kpad, dtype=F16, device=self.dev)
-        for (h, w, _), members in groups.items():
-            whole = isinstance(members, torch.Tensor) or len(members) == B
-            batch = members.to(self.dev) if isinstance(members, torch.Tensor) else torch.stack([t.to(self.dev) for _, t in members])
-            if batch.stride(3) != 1 or batch.stride(2) != 3:
-                batch = batch.contiguous()
-            rows = a16 if whole else torch.empty(len(members) * P, self.kpad, dtype=F16, device=self.dev)
-            ops.clip_patchify_u8(batch, rows, self.S, self.ps, mean, std, crop=crop, kpad=self.kpad)
-            if not whole:
-                a16.view(B, P, self.kpad)[torch.tensor([i for i, _ in members], device=self.dev)] = rows.view(len(members), P, self.kpad)
-        return a16
-
-    def _encode(self, a16: torch.Tensor, B: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The tower on the patch rows a16 [B * (T - 1), kpad]."""
-        dev, C, T = self.dev, self.C, self.T
-        pe = torch.empty(B * (T - 1), C, dtype=F32, device=dev)
-        ops.gemm(a16, self.wp, pe, workspace=self.ws)
-        e = torch.empty(B * T, C, dtype=F32, device=dev)
-        ops.clip_embed_patches(pe, self.cls, self.pos, e, T)
-        h0 = torch.empty(B * T, C, dtype=F16, device=dev)
-        ops.layernorm(e, self.pre[0], self.pre[1], h0, self.eps)          # pre_layrnorm: the stream the first layer reads and adds to
-        x = torch.empty(B * T, C, dtype=F32, device=dev)
-        self.stack.run(h0, x, B, T, False)
-        p16 = torch.empty(B, C, dtype=F16, device=dev)
-        ops.layernorm(x.view(B, T * C)[:, :C], self.post[0], self.post[1], p16, self.eps)      # post_layernorm on the class rows
-        embeds = torch.empty(B, self.pdim, dtype=F32, device=dev)
+            a16 = self.tower.patch_rows(images, mean, std, in_scale, in_shift)
+        B = a16.shape[0] // (self.T - 1)
+        x, p16 = self.tower.encode(a16, B)
+        embeds = torch.empty(B, self.pdim, dtype=F32, device=self.dev)
         ops.gemm(p16, self.proj, embeds, workspace=self.ws)
-        return embeds, x.view(B, T, C)
+        return embeds, x.view(B, self.T, self.C)
 
     def encode_pixels(self, pixel_values: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """CLIPVisionModelWithProjection.forward(pixel_values): already preprocessed [B,3,S,S] input, cut into patches as it is (the resampling
@@ -603,20 +424,27 @@ def vae_param_shapes(block_out_channels=(128, 256, 512, 512), layers_per_block: 
     return out
 
 
+def _clip_layer_shapes(prefix: str, C: int, I: int, n: int) -> Dict[str, Tuple[int, ...]]:
+    """`{prefix}encoder.layers.{0..n-1}.*` of a CLIP tower, in transformers' order."""
+    out: Dict[str, Tuple[int, ...]] = {}
+    for i in range(n):
+        p = f"{prefix}encoder.layers.{i}."
+        for name in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            out[f"{p}self_attn.{name}.weight"], out[f"{p}self_attn.{name}.bias"] = (C, C), (C,)
+        out[p + "layer_norm1.weight"], out[p + "layer_norm1.bias"] = (C,), (C,)
+        out[p + "mlp.fc1.weight"], out[p + "mlp.fc1.bias"] = (I, C), (I,)
+        out[p + "mlp.fc2.weight"], out[p + "mlp.fc2.bias"] = (C, I), (C,)
+        out[p + "layer_norm2.weight"], out[p + "layer_norm2.bias"] = (C,), (C,)
+    return out
+
+
 def clip_text_param_shapes(vocab_size: int = 49408, hidden_size: int = 768, intermediate_size: int = 3072, num_hidden_layers: int = 12,
                            max_position_embeddings: int = 77) -> Dict[str, Tuple[int, ...]]:
     """Names (with transformers 4.x's `text_model.` prefix) and shapes of CLIPTextModel's parameters."""
     C, I = hidden_size, intermediate_size
     out = {"text_model.embeddings.token_embedding.weight": (vocab_size, C),
            "text_model.embeddings.position_embedding.weight": (max_position_embeddings, C)}
-    for i in range(num_hidden_layers):
-        p = f"text_model.encoder.layers.{i}."
-        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
-            out[f"{p}self_attn.{n}.weight"], out[f"{p}self_attn.{n}.bias"] = (C, C), (C,)
-        out[p + "layer_norm1.weight"], out[p + "layer_norm1.bias"] = (C,), (C,)
-        out[p + "mlp.fc1.weight"], out[p + "mlp.fc1.bias"] = (I, C), (I,)
-        out[p + "mlp.fc2.weight"], out[p + "mlp.fc2.bias"] = (C, I), (C,)
-        out[p + "layer_norm2.weight"], out[p + "layer_norm2.bias"] = (C,), (C,)
+    out.update(_clip_layer_shapes("text_model.", C, I, num_hidden_layers))
     out["text_model.final_layer_norm.weight"], out["text_model.final_layer_norm.bias"] = (C,), (C,)
     return out
 
@@ -629,14 +457,7 @@ def clip_vision_param_shapes(hidden_size: int = 768, intermediate_size: int = 30
            "vision_model.embeddings.patch_embedding.weight": (C, 3, patch_size, patch_size),
            "vision_model.embeddings.position_embedding.weight": ((image_size // patch_size) ** 2 + 1, C),
            "vision_model.pre_layrnorm.weight": (C,), "vision_model.pre_layrnorm.bias": (C,)}
-    for i in range(num_hidden_layers):
-        p = f"vision_model.encoder.layers.{i}."
-        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
-            out[f"{p}self_attn.{n}.weight"], out[f"{p}self_attn.{n}.bias"] = (C, C), (C,)
-        out[p + "layer_norm1.weight"], out[p + "layer_norm1.bias"] = (C,), (C,)
-        out[p + "mlp.fc1.weight"], out[p + "mlp.fc1.bias"] = (I, C), (I,)
-        out[p + "mlp.fc2.weight"], out[p + "mlp.fc2.bias"] = (C, I), (C,)
-        out[p + "layer_norm2.weight"], out[p + "layer_norm2.bias"] = (C,), (C,)
+    out.update(_clip_layer_shapes("vision_model.", C, I, num_hidden_layers))
     out["vision_model.post_layernorm.weight"], out["vision_model.post_layernorm.bias"] = (C,), (C,)
     out["visual_projection.weight"] = (projection_dim, C)
     return out

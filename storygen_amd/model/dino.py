@@ -14,6 +14,7 @@ from typing import Optional
 
 import torch
 
+from ..clip_score import clip_grid_tokens
 from ..dino import DinoVitEngine, dino_param_shapes
 from ..encoders import check_clip_dims_wide, init_state
 from .encoders import SD, _HipModule
@@ -29,10 +30,10 @@ class DinoVisionTransformer(_HipModule):
             raise TypeError(f"DinoVisionTransformer: unknown config keys {unknown}")
         cfg = OrderedDict(DINO_DEFAULTS)
         cfg.update(config)
-        S, ps = int(cfg["img_size"]), int(cfg["patch_size"])
-        if S <= 0 or ps <= 0 or S % ps or (3 * ps * ps) % 4:
-            raise ValueError(f"DinoVisionTransformer: img_size {S} must be a multiple of patch_size {ps}, and 3 * patch_size^2 of 4")
-        check_clip_dims_wide("DinoVisionTransformer", int(cfg["embed_dim"]), int(cfg["num_heads"]), (S // ps) ** 2 + 1)
+        S, ps, tokens = clip_grid_tokens(cfg, "DinoVisionTransformer", "img_size")
+        if (3 * ps * ps) % 4:
+            raise ValueError(f"DinoVisionTransformer: 3 * patch_size^2 = {3 * ps * ps} must be a multiple of 4")
+        check_clip_dims_wide("DinoVisionTransformer", int(cfg["embed_dim"]), int(cfg["num_heads"]), tokens)
         self._config = FrozenConfig(cfg).freeze()
         self._shapes = dino_param_shapes(cfg["embed_dim"], cfg["depth"], ps, S, cfg["mlp_ratio"])
         # init_state's rules by name: `pos_embed` / `cls_token` are tables like DINO's trunc_normal_(std=.02) ones

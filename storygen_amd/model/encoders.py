@@ -26,6 +26,7 @@ from typing import Dict, Optional
 
 import torch
 
+from ..clip_score import clip_grid_tokens
 from ..encoders import (ClipTextEngine, ClipVisionEngine, VaeEngine, check_clip_dims, clip_text_param_shapes, clip_vision_param_shapes, init_state,
                         vae_param_shapes)
 from .unet_2d_condition import CONFIG_NAME, SAFETENSORS_NAME, WEIGHTS_NAME, FrozenConfig
@@ -353,12 +354,10 @@ CLIP_VISION_DEFAULTS = OrderedDict(hidden_size=768, intermediate_size=3072, proj
 def check_clip_vision_config(cfg, who: str = "CLIPVisionModelWithProjection") -> None:
     """Refuses, on the host, what the kernels cannot run: a patch grid that does not tile the image, more than 128 tokens or a head dim above
     64 (ViT-H/14), an activation other than quick_gelu / gelu."""
-    S, ps = int(cfg["image_size"]), int(cfg["patch_size"])
     if cfg.get("num_channels", 3) != 3:
         raise ValueError(f"{who}: num_channels must be 3")
-    if S <= 0 or ps <= 0 or S % ps:
-        raise ValueError(f"{who}: image_size {S} is not a multiple of patch_size {ps}")
-    check_clip_dims(who, int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), (S // ps) ** 2 + 1)
+    _, ps, tokens = clip_grid_tokens(cfg, who)
+    check_clip_dims(who, int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), tokens)
     if (3 * ps * ps) % 8 or int(cfg["projection_dim"]) % 8:
         raise ValueError(f"{who}: 3 * patch_size^2 and projection_dim must be multiples of 8")
     if cfg["hidden_act"] not in ("quick_gelu", "gelu"):

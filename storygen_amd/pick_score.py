@@ -26,8 +26,8 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import ops
-from .clip_score import TEXT_KEYS, VISION_KEYS, _cfg, _sub, as_nchw
-from .encoders import ClipTextEngine, ClipVisionEngine, check_clip_dims, check_clip_dims_wide, is_uint8_images
+from .clip_score import TEXT_KEYS, VISION_KEYS, _cfg, as_nchw, build_clip_towers, clip_grid_tokens
+from .encoders import check_clip_dims, check_clip_dims_wide, is_uint8_images
 
 SD = Dict[str, torch.Tensor]
 
@@ -44,10 +44,8 @@ def split_config(config, who: str = "PickScorer") -> Tuple[dict, dict]:
 
 def check_pick_config(vc: dict, tc: dict, who: str = "PickScorer") -> None:
     """Refuses on the host what the kernels cannot run (sg_attn_enc_f16 for the image tower, sg_attn_small_f16 for the text tower)."""
-    S, ps = int(vc["image_size"]), int(vc["patch_size"])
-    if S <= 0 or ps <= 0 or S % ps:
-        raise ValueError(f"{who}: image_size {S} is not a multiple of patch_size {ps}")
-    check_clip_dims_wide(f"{who} (image tower)", int(vc["hidden_size"]), int(vc["num_attention_heads"]), (S // ps) ** 2 + 1)
+    _, ps, tokens = clip_grid_tokens(vc, who)
+    check_clip_dims_wide(f"{who} (image tower)", int(vc["hidden_size"]), int(vc["num_attention_heads"]), tokens)
     if (3 * ps * ps) % 4:
         raise ValueError(f"{who}: 3 * patch_size^2 = {3 * ps * ps} must be a multiple of 4")
     check_clip_dims(f"{who} (text tower)", int(tc["hidden_size"]), int(tc["num_attention_heads"]), int(tc.get("max_position_embeddings", 77)))
@@ -67,20 +65,10 @@ class PickScorer:
         check_pick_config(vc, tc)
         if "logit_scale" not in state_dict:
             raise KeyError("PickScorer: the state dict has no logit_scale (CLIPModel naming)")
-        if not any(k.startswith("text_model.") for k in state_dict) or "text_projection.weight" not in state_dict:
-            raise KeyError("PickScorer: the state dict has no text tower (text_model.* and text_projection.weight, CLIPModel naming)")
-        if not any(k.startswith("vision_model.") for k in state_dict) or "visual_projection.weight" not in state_dict:
-            raise KeyError("PickScorer: the state dict has no image tower (vision_model.* and visual_projection.weight, CLIPModel naming)")
         self.dev = torch.device(device)
         self.in_scale, self.in_shift = float(in_scale), float(in_shift)
         self.logit_scale = state_dict["logit_scale"].detach().to(self.dev, torch.float32).reshape(())
-        self.vision = ClipVisionEngine(_sub(state_dict, ("vision_model.", "visual_projection.")), self.dev,
-                                       heads=int(vc["num_attention_heads"]), eps=float(vc.get("layer_norm_eps", 1e-5)),
-                                       hidden_act=vc.get("hidden_act", "quick_gelu"), image_size=int(vc["image_size"]), wide=True)
-        self.text = ClipTextEngine(_sub(state_dict, ("text_model.", "text_projection.")), self.dev, heads=int(tc["num_attention_heads"]),
-                                   eps=float(tc.get("layer_norm_eps", 1e-5)), hidden_act=tc.get("hidden_act", "quick_gelu"))
-        if self.text.proj.shape[0] != self.vision.pdim:
-            raise ValueError(f"PickScorer: text projection {self.text.proj.shape[0]} and image projection {self.vision.pdim} differ")
+        self.vision, self.text = build_clip_towers(state_dict, vc, tc, self.dev, True, "PickScorer")
 
     def image_features(self, images) -> torch.Tensor:
         """Projected image embeddings, fp32 [N, projection_dim] on the device (not normalised).  images: the pipeline's output_type="np" frames
