@@ -183,15 +183,26 @@ size_t sg_gemm_workspace_bytes(int32_t M, int32_t N, int32_t split_k);
  * through a multi-stage pipeline; x_padded = 0 reads an unpadded [B, H, W, Cin] tensor with bounds checks.
  * Operand size (32-bit byte offsets, as for sg_gemm_desc): (pixels - 1) * ldx + Cin <= 2^31 elements, where pixels =
  * B * (H + 2) * (W + 2) with x_padded and B * H * W without, and Cout * 9 * Cin <= 2^31; else SG_EINVAL.
+ * upsample2x = 2, the phase form: the same result as upsample2x = 1 computed as FOUR 2x2 convolutions of the input-resolution image, one
+ * per output parity (a, b) = (oy & 1, ox & 1): after nearest-2x upsampling the taps ky of output row 2i + a read source rows
+ * i - 1 (ky = 0), i (ky = 1, 2) for a = 0 and i (ky = 0, 1), i + 1 (ky = 2) for a = 1, likewise the columns.  `w` is then
+ * [4][Cout][2][2][Cin]: phase 2a + b, tap (ty, tx) = the sum of the 3x3 taps that read source pixel (i - 1 + a + ty, j - 1 + b + tx)
+ * (fp32 sums rounded to fp16 once: storygen_amd/repack.py upsample_phase_pack), and the contraction is 4 Cin long instead of 9 Cin —
+ * 4/9 of the multiply-adds; the result differs from upsample2x = 1 by that one rounding of the weights.  Needs x_padded = 1 and
+ * stride 1, takes bias but neither rowbias nor res1 (SG_EINVAL); stats, split_k and defer_reduce as otherwise (partials, y and the
+ * workspace keep their layouts; a statistics partial of the fused epilogue covers the rows of one row tile, which lie in one phase).
+ * A row tile must lie inside one phase image: a descriptor for which no tile of the LDS-DMA kernels divides H * W (or whose tile
+ * hint does not) has no phase-form launch, SG_EUNSUP from every entry point and query — the caller runs upsample2x = 1 instead.
+ * Cout * 16 * Cin <= 2^31.
  */
 typedef struct sg_conv3x3_desc {
     const sg_half* x;  int64_t ldx;   /* [B, H, W, Cin], pixel stride ldx */
-    const sg_half* w;                 /* [Cout, 3, 3, Cin] */
+    const sg_half* w;                 /* [Cout, 3, 3, Cin]; upsample2x = 2: [4, Cout, 2, 2, Cin] */
     void*          y;  int64_t ldy;   /* [B, Ho, Wo, Cout], pixel stride ldy; fp16, or fp32 with SG_F_OUT_F32 */
     int32_t B, H, W, Cin, Cout;
     int32_t flags;                    /* SG_F_OUT_F32 | SG_F_RES1_F32 */
     int32_t stride;                   /* 1 or 2 */
-    int32_t upsample2x;               /* 0 or 1 (then stride must be 1) */
+    int32_t upsample2x;               /* 0, 1 or 2 = the phase form (1, 2: stride must be 1) */
     int32_t x_padded;                 /* 0 or 1, see above */
     const sg_half* bias;              /* [Cout] or NULL */
     const float*   rowbias; int64_t rowbias_ld;   /* fp32 [B, rowbias_ld] or NULL */

@@ -34,6 +34,14 @@
 //     reduces them in slice order and applies the epilogue (deterministic, no atomics).  An in-launch reduction by the
 //     last-arriving slice (agent-scope release / acquire + ticket counter) was built and measured in round 2: the release
 //     fence behind 64 KB of freshly written partials costs more (+8..13 us per launch) than the kernel boundary it removes.
+//   * the upsampling convolution (nearest 2x + 3x3) also exists as FOUR 2x2 phase convolutions (sg_conv3x3_desc.upsample2x = 2,
+//     mma_phase_kernel = mma_pipe_body with PH): after the upsampling the three taps of a row fall on two source rows, so each output
+//     parity (a, b) is a 2x2 convolution of the input-resolution image on tap sums packed with the weights — K = 4 Cin instead of
+//     9 Cin.  Rows are ordered (sample, phase, i, j); a row tile lies inside one phase (the planner only takes tiles that divide H W,
+//     else SG_EUNSUP and the caller keeps upsample2x = 1), which picks its weight panel and tap origin; the epilogue maps a row to its
+//     output pixel (epi_out_row), so y, the split-K partial tiles and the GroupNorm partials keep their layouts.  Measured per launch:
+//     0.47 - 0.62 of the 3x3 form at the 16x16 / 32x32 inputs, 0.90 at 8x8 batch 20, equal at 8x8 batch 3 (the weight stream, 16/9 of
+//     the bytes: the engine keeps the 3x3 form there) — profiles/r20b_per_shape.txt.
 // Round-2 mainloop experiments (4-/2-stage rings, spread DMA issue on the 256x128 tile, ping-pong wave groups, LDS-resident conv
 // patches, fat waves) were measured neutral or slower (HISTORY.md 5.2) and are no longer part of the library; `git log` has them.
 #include "common.h"
@@ -74,6 +82,9 @@ struct MmaParams {
     int M, N, K, KT;
     // conv geometry (CONV only): input [B,H,Wd,Cin] (pre-upsample), output [B,Ho,Wo,N]
     int H, Wd, Ho, Wo, cpt /* Cin/64 */, stride, ups, padded;
+    // phase form of the upsampling convolution (sg_conv3x3_desc.upsample2x = 2; the kernels take it as a template parameter): M = 4 B H Wd
+    // rows ordered (sample, phase 2a + b, i, j), K = 4 Cin, W = four [N][2][2][Cin] panels; Ho / Wo = H / Wd (one phase image), ups = 0
+    int phase;
     // epilogue
     int mode, flags;
     const f16* bias;
@@ -283,7 +294,20 @@ __device__ __forceinline__ void ln_out_store(const MmaParams& p, int gm, int blk
 // summed for ln_out, which partials meet for the GroupNorm statistics) sits under `if constexpr (WT == 2)`; the split-K store and the linear
 // phases (bias / LayerNorm fold, temb row, residuals, stores) are written once, on NQ row quads per lane.  (As a function of their own
 // — or even as a lambda called in place — those phases made the 8-wave 256x128 tile spill: profiles/r25a_gemm_epilogue_helpers_ab.txt.)
-template <int WGM, int WGN, int WT = 2, int WTM = WT>
+// Phase form of the upsampling convolution: logical row (sample s, phase 2a + b, i, j) of the launch is pixel (2i + a, 2j + b) of sample
+// s in the unchanged NHWC output — row s 4HW + (2i + a) 2W + 2j + b = s 4HW + a 2W + b + 2q + 2iW with q = iW + j.  Everything that is
+// addressed by row goes through it (the output and the split-K partial tiles: the second pass and a deferring consumer see the
+// layout of any other convolution); the host admits no row-addressed INPUT of the epilogue (residual, row bias) in this form.
+template <bool PH>
+__device__ __forceinline__ int epi_out_row(const MmaParams& p, int gm) {
+    if constexpr (!PH) return gm;
+    const int hw = p.Ho * p.Wo;
+    const int sp = (int)fd_div((unsigned)gm, p.fd_hw), q = gm - sp * hw;
+    const int i = (int)fd_div((unsigned)q, p.fd_wo);
+    return (sp >> 2) * 4 * hw + ((sp >> 1) & 1) * 2 * p.Wo + (sp & 1) + 2 * q + 2 * i * p.Wo;
+}
+
+template <int WGM, int WGN, int WT = 2, int WTM = WT, bool PH = false>
 __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x16 (&acc)[WTM][WT], f32x4 (&pre)[WT == 2 ? 16 : 4], u32x2& pbias,
                                            int m0, int n0, int z, int wave, int wm0, int wn, int lane) {
     constexpr int BN = 32 * WT * WGN, NW = WGM * WGN, NT = 64 * NW, NH = WT == 2 ? WTM / 2 : 1, NQ = WT == 2 ? 16 : 4;
@@ -391,7 +415,7 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
         for (int k = 0; k < NQ; ++k) {
             const int row = 4 * k + r0, gm = rowq + 4 * k;
             const float4 v = *reinterpret_cast<const float4*>(stg + row * EPI_PITCH + 4 * lc);
-            if (gm < p.M && col_ok) st_stream(wsz + (size_t)gm * p.N, f32x4{v.x, v.y, v.z, v.w});
+            if (gm < p.M && col_ok) st_stream(wsz + (size_t)epi_out_row<PH>(p, gm) * p.N, f32x4{v.x, v.y, v.z, v.w});
         }
         continue;
     }
@@ -517,7 +541,7 @@ __device__ __forceinline__ void epi_finish(const MmaParams& p, char* smem, f32x1
     for (int k = 0; k < NQ; ++k) {
         const int gm = rowq + 4 * k;
         if (gm < p.M && col_ok) {
-            store_out4(p, gm, colq, v[k]);
+            store_out4(p, epi_out_row<PH>(p, gm), colq, v[k]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { cs[e] += v[k][e]; cq2[e] = fmaf(v[k][e], v[k][e], cq2[e]); }
         }
@@ -807,8 +831,15 @@ __device__ __forceinline__ void slab_tail(F& slab, int nt) {
     if constexpr (Y > 0) slab_tail<Y - 1, S>(slab, nt);
 }
 
-template <int WGM, int WGN, bool CONV, bool PROF = false, int S = 3, int WT = 2, int WTMX = WT>
+template <int WGM, int WGN, bool CONV, bool PROF = false, int S = 3, int WT = 2, int WTMX = WT, bool PH = false>
 __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
+    // PH: the upsampling convolution as four 2x2 phase convolutions (MmaParams::phase).  After nearest-2x upsampling the three taps of a
+    // row fall on two source rows (likewise columns), so output parity (a, b) is a 2x2 convolution of the input-resolution image with
+    // tap sums as weights (repack.upsample_phase_pack): K = 4 Cin instead of 9 Cin.  Rows are ordered (sample, phase, i, j) and a tile
+    // lies inside ONE phase of one sample (the host plans only tiles that divide H W), so the tile's phase picks the weight panel and
+    // the tap origin (a, b) in the zero-bordered input; the gather itself is the plain stride-1 form on 2x2 taps.
+    static_assert(!PH || (CONV && !PROF), "the phase form is a convolution");
+    constexpr int TAPS = PH ? 2 : 3;
     // PROF (SG_BUILD_EXPERIMENTS): s_memtime stamps around the phases of every slab, summed per wave (sg_debug_gemm_anatomy /
     // _conv_anatomy): [0] slabs [1] vmcnt wait [2] barrier [3] first fragment reads + k-step 0 [4] k-step 1 up to the DMA issue
     // [5] DMA issue [6] rest of the slab [7] prologue (entry -> loop) [8] epilogue (loop end -> exit)
@@ -878,7 +909,9 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
     // of a row — either order is a plain offset, nothing is repacked.
     // GEMM: slab kt starts at element kt * 64 of both operands.
     auto w_koff = [&](int kt) __attribute__((always_inline)) -> long {
-        if constexpr (CONV) {
+        if constexpr (PH) {
+            return (long)(kt & 3) * p.cpt * BK + (long)(kt >> 2) * BK;  // slab kt = (channel block kt / 4, tap kt % 4)
+        } else if constexpr (CONV) {
             const int cc = (kt * 7282) >> 16, tap = kt - 9 * cc;        // kt / 9 for kt < 3 000 (validated on the host)
             return (long)tap * p.cpt * BK + (long)cc * BK;
         } else {
@@ -886,9 +919,11 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
         }
     };
     const LdsRef lds = lds_ref(smem);
+    // (phase form: the weight panel of the tile's phase — [phase][N][2][2][Cin], a row of a panel is ldw = 4 Cin long)
+    const f16* const Wb = PH ? p.W + (long)(fd_div((unsigned)m0, p.fd_hw) & 3u) * p.N * p.ldw : p.W;
     auto issue_w = [&](long koff, int stage, int sel = -1) __attribute__((always_inline)) {
         const LdsRef sB = lds + (stage * STAGE + A_BYTES + wave * 1024);
-        const f16* Wt = p.W + koff;
+        const f16* Wt = Wb + koff;
 #pragma unroll
         for (int i = 0; i < B_IT; ++i)
             if (sel < 0 || ((A_IT + i) & 3) == sel) glds16(Wt, w_off[i], sB + i * ISTR);
@@ -908,7 +943,13 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
             const int oy = (int)fd_div((unsigned)rem, p.fd_wo), ox = rem - oy * p.Wo;
             const long img = (long)b * (p.H + 2) * wp;
             // padded input pixel of tap (ky, kx): row ((oy*stride - 1 + ky) >> ups) + 1, column likewise
-            if (!p.ups) {
+            if constexpr (PH) {
+                // b = sample * 4 + phase 2a + b, (oy, ox) = (i, j): tap (ty, tx) reads padded pixel (i + a + ty, j + b + tx) — at most
+                // row H + 1 / column Wd + 1 of the [H + 2, Wd + 2] bordered image
+                const long simg = (long)(b >> 2) * (p.H + 2) * wp;
+                a_off[i] = 2u * (unsigned)((simg + (long)(oy + ((b >> 1) & 1)) * wp + ox + (b & 1)) * p.lda + lc * 8);
+                a_par[i] = 0;
+            } else if (!p.ups) {
                 a_off[i] = 2u * (unsigned)((img + (long)(oy * p.stride) * wp + ox * p.stride) * p.lda + lc * 8);
                 a_par[i] = 0;
             } else {
@@ -929,7 +970,11 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
         ABase r;
         r.ky = r.kx = 0;
         r.wk = w_koff(kt);
-        if constexpr (CONV) {
+        if constexpr (PH) {
+            const int cc = kt >> 2, ky = (kt >> 1) & 1, kx = kt & 1;
+            r.ky = ky; r.kx = kx;
+            r.At = p.A + ((long)(ky * wp + kx) * p.lda + cc * BK);
+        } else if constexpr (CONV) {
             const int cc = (kt * 7282) >> 16, tap = kt - 9 * cc;
             const int ky = (tap * 11) >> 5, kx = tap - ky * 3;           // tap / 3 for tap < 9
             r.ky = ky; r.kx = kx;
@@ -942,7 +987,7 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
     auto a_emit = [&](const ABase& ab, int stage, int sel) __attribute__((always_inline)) {
         const LdsRef sA = lds + (stage * STAGE + wave * 1024);
         if constexpr (CONV) {
-            if (!p.ups) {
+            if (PH || !p.ups) {
 #pragma unroll
                 for (int i = 0; i < A_IT; ++i)
                     if (sel < 0 || (i & 3) == sel) glds16(ab.At, a_off[i], sA + i * ISTR);
@@ -974,19 +1019,20 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
     }
     // taps innermost: one pixel right per slab; after column 2 one row down and back to column 0; after tap 8 back to tap 0 of the
     // next channel block.  (Nearest-2x upsampling: the pixel offset comes from (ky, kx) in a_emit, only the channel block moves here.)
+    // (Phase form: the same walk over TAPS x TAPS = 2 x 2 taps.)
     const long it_px = CONV && !p.ups ? (long)p.lda : 0;
-    const long it_dy = CONV && !p.ups ? (long)(wp - 3) * p.lda : 0;
-    const long it_dc = CONV ? (p.ups ? 0 : -3L * wp * p.lda) + BK : 0;
-    const long it_wtap = CONV ? (long)p.cpt * BK : BK, it_wdc = CONV ? BK - 9L * p.cpt * BK : 0;
+    const long it_dy = CONV && !p.ups ? (long)(wp - TAPS) * p.lda : 0;
+    const long it_dc = CONV ? (p.ups ? 0 : -(long)TAPS * wp * p.lda) + BK : 0;
+    const long it_wtap = CONV ? (long)p.cpt * BK : BK, it_wdc = CONV ? BK - (long)(TAPS * TAPS) * p.cpt * BK : 0;
     auto a_next = [&]() __attribute__((always_inline)) {
         ABase r;
         r.At = p.A + it_off; r.ky = it_ky; r.kx = it_kx; r.wk = it_wk;
         it_wk += it_wtap;
         if constexpr (CONV) {
             it_off += it_px;
-            if (++it_kx == 3) {
+            if (++it_kx == TAPS) {
                 it_kx = 0; it_off += it_dy;
-                if (++it_ky == 3) { it_ky = 0; it_off += it_dc; it_wk += it_wdc; }
+                if (++it_ky == TAPS) { it_ky = 0; it_off += it_dc; it_wk += it_wdc; }
             }
         } else {
             it_off += BK;
@@ -1121,7 +1167,7 @@ __device__ __forceinline__ void mma_pipe_body(const MmaParams& p, char* smem) {
     for (int it = 0; it < nsteady; it += S) slab_seq<0, S, YS>(slab, it, nsteady);
     slab_tail<TAIL - 1, S>(slab, nt);
     if (nt <= 0) prefetch();
-    epi_finish<WGM, WGN, WT, WTM>(p, smem, acc, pre_f, pre_bias, m0, n0, z, wave, wm, wn, lane);
+    epi_finish<WGM, WGN, WT, WTM, PH>(p, smem, acc, pre_f, pre_bias, m0, n0, z, wave, wm, wn, lane);
     if constexpr (PROF) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         stamp(8);
@@ -1138,6 +1184,14 @@ template <int WGM, int WGN, bool CONV, int S = 3>
 __global__ __launch_bounds__(64 * WGM * WGN) void mma_pipe_kernel(const MmaParams p) {
     __shared__ __attribute__((aligned(16))) char smem[pipe_smem_bytes<WGM, WGN, S>()];
     mma_pipe_body<WGM, WGN, CONV, false, S>(p, smem);
+}
+
+// The upsampling convolution as four 2x2 phase convolutions (mma_pipe_body, PH): a kernel of its own, so that the instantiations above
+// keep their names and their code.  Only the tile classes the UNet's three Upsample2D launches are planned on (phase_tile_ok).
+template <int WGM, int WGN>
+__global__ __launch_bounds__(64 * WGM * WGN) void mma_phase_kernel(const MmaParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[pipe_smem_bytes<WGM, WGN, 3>()];
+    mma_pipe_body<WGM, WGN, true, false, 3, 2, 2, true>(p, smem);
 }
 
 // The "fat wave" form (round 6): WGM x WGN waves of 128x64 on a 2-stage ring — 512x128 (4x2) and 256x256 (2x4) tiles for
@@ -1446,13 +1500,19 @@ struct Plan {
 };
 
 
+// Tile classes mma_phase_kernel is instantiated for (launch_plan): what the UNet's Upsample2D launches are planned on — 256x128 and
+// 128x128 at the 16x16 / 32x32 inputs, the 64-row tiles at the 8x8 input (H W = 64).
+bool phase_tile_ok(int bm, int bn) { return (bm == 256 && bn == 128) || (bm == 128 && bn == 128) || (bm == 64 && (bn == 128 || bn == 64)); }
+
 // Cost model (cycles at ~2.4 GHz).  Measured on MI355X (tools/bench_gemm.py): a CU pulls operand slabs from L2 into
 // LDS at ~18.5 B/cycle however many waves ask (L1 miss-level parallelism x L2 latency), so a launch is bound by
 //   t_bw   = (blocks a CU must run) x (bytes one block streams) / 18.5      — total bytes over the ACTIVE CUs, or by
 //   t_mfma = (waves per SIMD) x slabs x 512                                  — 16 MFMAs of 32 cycles per 64-deep slab,
 // plus a fixed prologue/epilogue.  Splitting K does not add operand bytes but multiplies the CUs that share them,
 // which is what small-M layers need; it costs a second launch that re-reads the fp32 partial tiles.
-Plan choose_plan(int M, int N, int KT, int force_split, int max_ws_split, bool pipe, int hint_bm, int hint_bn) {
+// row_div > 0 (phase form of the upsampling convolution): only tiles whose height divides row_div = H W, so that a row tile lies inside
+// one phase of one sample; no such candidate (or a hint that is none) leaves best.bm = 0 and plan_mma answers SG_EUNSUP.
+Plan choose_plan(int M, int N, int KT, int force_split, int max_ws_split, bool pipe, int hint_bm, int hint_bn, int row_div = 0) {
     static const int cand_pipe[6][2] = {{256, 128}, {128, 128}, {256, 64}, {128, 64}, {64, 128}, {64, 64}};
     static const int cand_gen[1][2] = {{128, 128}};      // the register-staged kernel is a cold path: one tile shape
     static const int split_opts[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16};
@@ -1470,6 +1530,7 @@ Plan choose_plan(int M, int N, int KT, int force_split, int max_ws_split, bool p
         const int bm = pipe ? cand_pipe[ci][0] : cand_gen[ci][0], bn = pipe ? cand_pipe[ci][1] : cand_gen[ci][1];
         if (pipe && o.tile_m && (bm != o.tile_m || bn != o.tile_n)) continue;
         if (pipe && !o.tile_m && hint_bm && (bm != hint_bm || bn != hint_bn)) continue;
+        if (row_div > 0 && (row_div % bm != 0 || !phase_tile_ok(bm, bn))) continue;
         const long tiles = (long)sg_cdiv(M, bm) * sg_cdiv(N, bn);
         const double waves_per_block = pipe ? (bm / 64) * (bn / 64) : 4.0;
         const double mfma_per_slab = pipe ? 512.0 : 512.0 * (bm / 64.0) * (bn / 64.0) / 4.0;
@@ -1490,6 +1551,7 @@ Plan choose_plan(int M, int N, int KT, int force_split, int max_ws_split, bool p
         }
     }
     // (best_cost == 1e300: a development tile that is none of the candidates — `best` still holds a tile its family has)
+    if (row_div > 0 && best_cost == 1e300) best.bm = best.bn = 0;
     return best;
 }
 
@@ -1570,6 +1632,12 @@ bool asks_lat(TileHint h) { return (h.waves == 4 && h.bm == 64 && h.bn == 64) ||
 template <bool CONV>
 Plan choose_family(const MmaParams& p, const PlanRequest& rq, TileHint hint, bool pipe, int max_ws_split) {
     const SgOptions& o = sg_options();
+    if (CONV && p.phase) {
+        // phase form: the 64x64-per-wave LDS-DMA tiles that divide a phase image, chosen by the cost model on M x N x 4 Cin (a hint for
+        // the 128x64- or 32x32-per-wave kernels, a development tile or the register-staged kernel: no such launch, SG_EUNSUP)
+        if (!pipe || o.tile_m || p.prof || asks_fat(hint) || asks_lat(hint)) return Plan{0, 0, 1, FAM_PIPE};
+        return choose_plan(p.M, p.N, p.KT, rq.force_split, max_ws_split, true, hint.bm, hint.bn, p.Ho * p.Wo);
+    }
     const bool fat_ok = pipe && !p.prof && !o.tile_m && rq.force_split <= 1 && (p.mode == SG_EPI_LINEAR || p.mode == SG_EPI_GEGLU);
     if (asks_fat(hint)) {
         if (fat_ok) return Plan{hint.bm, hint.bn, 1, FAM_FAT};
@@ -1596,9 +1664,13 @@ Plan choose_family(const MmaParams& p, const PlanRequest& rq, TileHint hint, boo
 // the former M-first walk).  Development option no_nmajor = 1: N first everywhere (group_m = 1).
 template <bool CONV>
 int choose_group_m(const MmaParams& p, int splits) {
-    const double a_bytes = CONV ? 2.0 * p.M * (p.K / 9) * (p.stride == 1 && !p.ups ? 1.0 : (p.ups ? 0.25 : 4.0)) : 2.0 * p.M * p.K;
+    // (phase form: K = 4 Cin, the input is a quarter of the M rows; w_panel is a column tile's panel of ONE phase — consecutive row tiles
+    // run through the phases, tiles_m / (4 B) = H W / bm tiles each, and every phase among them brings its own panel)
+    const double a_bytes = CONV ? (p.phase ? 2.0 * p.M * (p.K / 4) * 0.25
+                                           : 2.0 * p.M * (p.K / 9) * (p.stride == 1 && !p.ups ? 1.0 : (p.ups ? 0.25 : 4.0))) : 2.0 * p.M * p.K;
     const double w_bytes = 2.0 * p.N * p.K;
     const double a_panel = a_bytes / p.tiles_m, w_panel = w_bytes / p.tiles_n;
+    const int tiles_per_phase = CONV && p.phase ? (int)((long)p.tiles_m * p.Ho * p.Wo / p.M) : 0;
     const int wave_tiles = splits >= 32 ? 1 : 32 / splits;
     int best = 1;
     double best_bytes = 1e300;
@@ -1615,7 +1687,8 @@ int choose_group_m(const MmaParams& p, int splits) {
             if (rows > p.tiles_m) rows = p.tiles_m;
             cols = p.tiles_n;
         }
-        const double bytes = rows * a_panel + cols * w_panel;
+        const int panels = tiles_per_phase > 0 ? (rows + tiles_per_phase - 1) / tiles_per_phase : 1;
+        const double bytes = rows * a_panel + cols * w_panel * panels;
         if (bytes <= best_bytes) { best_bytes = bytes; best = gm; }
     }
     return sg_options().no_nmajor ? 1 : best;
@@ -1649,6 +1722,10 @@ int plan_mma(MmaParams& p, const PlanRequest& rq, Plan& pl) {
     const size_t per_split = (size_t)p.M * p.N * 4;
     const int max_ws_split = rq.ws ? (int)(rq.ws_bytes / per_split > 64 ? 64 : rq.ws_bytes / per_split) : 1;
     pl = choose_family<CONV>(p, rq, apply_big_m(rq.hint, p.M, pipe), pipe, max_ws_split);
+    if (CONV && p.phase && (pl.bm == 0 || (p.Ho * p.Wo) % pl.bm != 0 || !phase_tile_ok(pl.bm, pl.bn)))
+        return sg_set_error(SG_EUNSUP, "%s: no phase-form launch for this descriptor (a row tile of the LDS-DMA kernels must divide the "
+                            "%d pixels of the %dx%d input, and be one mma_phase_kernel is built for): use upsample2x = 1", rq.name,
+                            p.Ho * p.Wo, p.H, p.Wd);
     if (pl.splits > 1 && (rq.ws == nullptr || rq.ws_bytes < per_split * pl.splits))
         return sg_set_error(SG_EINVAL, "%s: split_k=%d needs %zu workspace bytes, got %zu", rq.name, pl.splits, per_split * pl.splits,
                             rq.ws_bytes);
@@ -1706,7 +1783,12 @@ int launch_plan(const MmaParams& p, const Plan& pl, hipStream_t st, const char* 
     if (p.defer && pl.splits <= 1)
         return sg_set_error(SG_EINVAL, "%s: defer_reduce needs a split-K launch (query sg_conv3x3_planned_splits first)", name);
     const dim3 grid(pl.grid), block(pl.threads);
-    if (pl.family == FAM_FAT) {
+    if (CONV && p.phase) {                  // plan_mma admitted the tile (phase_tile_ok)
+        if (pl.bm == 256) hipLaunchKernelGGL((mma_phase_kernel<4, 2>), grid, block, 0, st, p);
+        else if (pl.bm == 128) hipLaunchKernelGGL((mma_phase_kernel<2, 2>), grid, block, 0, st, p);
+        else if (pl.bn == 128) hipLaunchKernelGGL((mma_phase_kernel<1, 2>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((mma_phase_kernel<1, 1>), grid, block, 0, st, p);
+    } else if (pl.family == FAM_FAT) {
         if (pl.bm == 512) hipLaunchKernelGGL((mma_fat_kernel<4, 2, CONV>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((mma_fat_kernel<2, 4, CONV>), grid, block, 0, st, p);
     } else if (pl.lat()) {
@@ -1846,7 +1928,13 @@ int conv_params(const sg_conv3x3_desc* d, MmaParams& p, const char* who) {
     SG_REQUIRE(d->Cin % 64 == 0, "%s: Cin (%d) must be a multiple of 64", who, d->Cin);
     SG_REQUIRE(d->Cout % 8 == 0, "%s: Cout (%d) must be a multiple of 8", who, d->Cout);
     SG_REQUIRE(d->stride == 1 || d->stride == 2, "%s: stride must be 1 or 2", who);
-    SG_REQUIRE(d->upsample2x == 0 || (d->upsample2x == 1 && d->stride == 1), "%s: upsample2x needs stride 1", who);
+    SG_REQUIRE(d->upsample2x >= 0 && d->upsample2x <= 2, "%s: upsample2x must be 0, 1 or 2", who);
+    SG_REQUIRE(d->upsample2x == 0 || d->stride == 1, "%s: upsample2x needs stride 1", who);
+    // phase form (upsample2x = 2): w is the packed [4][Cout][2][2][Cin]; LDS-DMA kernels only (zero-bordered input), and nothing in the
+    // epilogue that is READ by row (epi_out_row)
+    const bool ph = d->upsample2x == 2;
+    SG_REQUIRE(!ph || d->x_padded == 1, "%s: upsample2x = 2 (phase form) needs the zero-bordered input (x_padded = 1)", who);
+    SG_REQUIRE(!ph || (!d->res1 && !d->rowbias), "%s: upsample2x = 2 (phase form) takes bias only (no res1, no rowbias)", who);
     SG_REQUIRE(d->x_padded == 0 || d->x_padded == 1, "%s: x_padded must be 0 or 1", who);
     SG_REQUIRE(d->ldx % 8 == 0 && d->ldx >= d->Cin, "%s: bad ldx", who);
     SG_REQUIRE(sg_aligned16(d->x) && sg_aligned16(d->w), "%s: x/w must be 16-byte aligned", who);
@@ -1863,29 +1951,34 @@ int conv_params(const sg_conv3x3_desc* d, MmaParams& p, const char* who) {
         const int bord = d->x_padded ? 2 : 0;
         const long long rows = (long long)d->B * (d->H + bord), pixels = rows <= lim ? rows * (d->W + bord) : lim + 1;
         const long long x_span = pixels <= lim ? (pixels - 1) * (long long)d->ldx + d->Cin : lim + 1;
-        const long long w_span = (long long)d->Cout * 9 * d->Cin;
+        const long long w_span = (long long)d->Cout * (ph ? 16 : 9) * d->Cin;
         SG_REQUIRE(x_span <= lim,
                    "%s: input x spans %s%lld elements ((pixels - 1) * ldx + Cin%s); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)",
                    who, pixels <= lim ? "" : "more than ", x_span, d->x_padded ? ", zero border included" : "");
         SG_REQUIRE(w_span <= lim,
-                   "%s: weights w span %lld elements (Cout * 9 * Cin); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)", who, w_span);
+                   "%s: weights w span %lld elements (Cout * 9 * Cin; 16 in the phase form); the bound is 2^31 elements (4 GiB: 32-bit LDS-DMA byte offsets)", who, w_span);
     }
     SG_REQUIRE(9 * (d->Cin / 64) < 3000, "%s: Cin (%d) too large for the slab decode (kt / 9 by multiply-shift, kt < 3000)", who, d->Cin);
-    const int hin = d->H << d->upsample2x, win = d->W << d->upsample2x;
+    const int up = d->upsample2x ? 1 : 0;
+    const int hin = d->H << up, win = d->W << up;
     const int Ho = (hin + 2 - 3) / d->stride + 1, Wo = (win + 2 - 3) / d->stride + 1;
     p = MmaParams{};
     p.A = reinterpret_cast<const f16*>(d->x); p.lda = d->ldx;
-    p.W = reinterpret_cast<const f16*>(d->w); p.ldw = 9L * d->Cin;
+    p.W = reinterpret_cast<const f16*>(d->w); p.ldw = (ph ? 4L : 9L) * d->Cin;
     p.C = d->y; p.ldc = d->ldy;
-    p.M = d->B * Ho * Wo; p.N = d->Cout; p.K = 9 * d->Cin;
+    p.M = d->B * Ho * Wo; p.N = d->Cout; p.K = (ph ? 4 : 9) * d->Cin;
     p.H = d->H; p.Wd = d->W; p.Ho = Ho; p.Wo = Wo; p.cpt = d->Cin / 64; p.stride = d->stride; p.ups = d->upsample2x;
+    // phase form: M = 4 B H W rows in (sample, phase, i, j) order — the kernels decode a row against ONE phase image (Ho x Wo = H x W)
+    if (ph) { p.phase = 1; p.ups = 0; p.Ho = d->H; p.Wo = d->W; }
     p.padded = d->x_padded;
     p.mode = SG_EPI_LINEAR; p.flags = d->flags;
     p.bias = reinterpret_cast<const f16*>(d->bias);
     p.rowbias = d->rowbias; p.rowbias_ld = d->rowbias_ld; p.rows_per_batch = Ho * Wo;
     p.res1 = d->res1; p.ldr1 = d->ldr1;
     SG_REQUIRE(!d->stats || sg_aligned16(d->stats), "%s: stats alignment", who);
-    p.stats = d->stats; p.stats_batch_rows = Ho * Wo;
+    // (phase form: a partial of the fused epilogue is one row tile = rows of one phase of one sample; any equal split of a sample's rows
+    // serves the consumer, which adds the sums of a sample's partials)
+    p.stats = d->stats; p.stats_batch_rows = ph ? d->H * d->W : Ho * Wo;
     SG_REQUIRE(d->defer_reduce == 0 || (d->defer_reduce == 1 && !d->stats), "%s: defer_reduce is 0 or 1 and excludes stats", who);
     p.defer = d->defer_reduce;
     return check_tile_hint(who, d->tile_m, d->tile_n, d->tile_waves);

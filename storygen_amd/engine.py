@@ -33,7 +33,7 @@ import torch
 
 from . import ops
 from .arch import BlockSpec, ResnetSpec, UNetArch, XfSpec, feature_shapes
-from .repack import conv1x1_nk, conv3x3_krsc, conv_in_kn, ff_fused_pack, fold_layernorm, interleave_geglu
+from .repack import conv1x1_nk, conv3x3_krsc, conv_in_kn, ff_fused_pack, fold_layernorm, interleave_geglu, upsample_phase_pack
 
 F16 = torch.float16
 GN_EPILOGUE_STATS = True   # GroupNorm statistics from the producing conv / GEMM epilogues (False = every GroupNorm makes its own pass)
@@ -72,6 +72,14 @@ FF_SPLIT_MAX_TOKENS = 16384
 # (and one fp16 rounding of an intermediate) less per transformer block at C = 640 / 1280 (round 6; the 64x64 level runs the fused
 # feed-forward kernel instead).  False = the two GEMMs as written (A/B switch: bench.py --no-ff-proj-merge).
 FF_PROJ_MERGE = True
+# Upsample2D (nearest 2x + 3x3) as four 2x2 convolutions of the input-resolution image, one per output parity, on tap sums packed with
+# the weights (repack.upsample_phase_pack; sg_conv3x3_desc.upsample2x = 2): 4/9 of the multiply-adds, one more fp16 rounding of the
+# weights.  A launch the form does not fit (no row tile divides H W) keeps the 3x3 form.  False = the 3x3 form everywhere (A/B switch).
+UPSAMPLE_PHASES = True
+# ... from this many output rows (B * 2H * 2W) on.  Below, the launch is its weight stream and the pack is 16/9 of the 3x3 weights'
+# bytes: the 8x8 -> 16x16 launch of the batch-3 main pass (768 rows, 52 MB of packed weights) measured 42.2 us against 41.6 us in the
+# 3x3 form and stays there; the same level at batch 20 (5 120 rows) 150 against 168 us (profiles/r20b_per_shape.txt).
+UPSAMPLE_PHASES_MIN_ROWS = 1024
 LN_EPS = 1e-5         # torch.nn.LayerNorm default, as the reference constructs norm1..norm4 (model/attention.py:213-233)
 
 
@@ -189,6 +197,10 @@ class EngineWeights:
             if blk.sampler_prefix:
                 self.samplers[blk.sampler_prefix] = (conv3x3_krsc(g(f"{blk.sampler_prefix}.weight")),
                                                      g(f"{blk.sampler_prefix}.bias"))
+        # Upsample2D convolutions as four 2x2 phase convolutions (UPSAMPLE_PHASES): tap sums per output parity, [4, Cout, 2, 2, Cin].  The
+        # 3x3 weights above stay: a launch the phase form does not fit (ops.conv3x3_upsample) and the A/B switch run on them.
+        self.sampler_phases = {blk.sampler_prefix: upsample_phase_pack(g(f"{blk.sampler_prefix}.weight"))
+                               for blk in arch.up if blk.sampler_prefix}
         self.gn_out = (g("conv_norm_out.weight"), g("conv_norm_out.bias"))
         self.w_conv_out = conv3x3_krsc(g("conv_out.weight"))
         self.b_conv_out = g("conv_out.bias")
@@ -896,6 +908,14 @@ class UNetEngine:
         pbuf = self.padded[(lvl, h.shape[1])]
         ops.pad_cast(self._img(h, lvl), pbuf)
         kw = dict(stride=2 if down else 1, upsample2x=not down, bias=b, workspace=self.ws_split, x_padded=True)
+        # Upsample2D as four 2x2 phase convolutions where that form has a launch for this batch and level (asked on every call, like
+        # _defer_splits: host-only arithmetic that depends on process state); its statistics site is its own — the rows per partial
+        # are those of ITS plan
+        if not down and UPSAMPLE_PHASES and self.dev.type == "cuda" and out.shape[0] >= UPSAMPLE_PHASES_MIN_ROWS:
+            kwp = dict(kw, upsample2x=2)
+            wp = self.sampler_phases[prefix]
+            if ops.conv3x3_phases_fit(pbuf, wp, self._img(out, out_lvl), **kwp):
+                w, kw, prefix = wp, kwp, prefix + "#phases"
         return self._produce(prefix, out_lvl, out.shape[1], lambda s: ops.conv3x3(pbuf, w, self._img(out, out_lvl), stats=s, **kw),
                              lambda buf: ops.conv3x3_stats_rows(pbuf, w, self._img(out, out_lvl), stats=buf, **kw))
 

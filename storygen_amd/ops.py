@@ -20,6 +20,7 @@ lib = _lib.load()
 EPI_LINEAR = 0
 EPI_GEGLU = 1
 F_OUT_F32, F_RES1_F32, F_RES2_F32 = 1, 2, 4
+EUNSUP = -2           # SG_EUNSUP: a valid request the library has no launch for
 
 # Per-shape tile / split-K choices measured on an MI355X by tools/tune_tiles.py (storygen_amd/tuning/mi355x_tiles.json);
 # anything not listed uses the library's cost model.  TUNE_SINK: when set, every gemm/conv3x3 call appends its
@@ -305,6 +306,9 @@ def _report_plan(kind: str, d, nbytes: float, family: str, shape: str, second=No
         PLAN_SINK.append((_kernel_name(bm1, bn1, pipe1, False), wgs1 * threads1, b1, family, shape + " [2nd]"))
     else:
         bm, bn, _, wgs, threads, pipe = _plan_of(lib.sg_conv3x3_launch_plan if kind == "conv" else lib.sg_gemm_launch_plan, d)
+        if kind == "conv" and d.upsample2x == 2:
+            PLAN_SINK.append((f"mma_phase_kernel<{bm // 64}, {bn // 64}>", wgs * threads, nbytes, family, shape))
+            return
     PLAN_SINK.append((_kernel_name(bm, bn, pipe, kind == "conv"), wgs * threads, nbytes, family, shape))
 
 
@@ -407,9 +411,10 @@ def _conv_desc(x: torch.Tensor, w_krsc: torch.Tensor, out: torch.Tensor, *, stri
     B, H, W, Cin = x.shape
     if x_padded:
         H, W = H - 2, W - 2
-    Cout = w_krsc.shape[0]
-    if tuple(w_krsc.shape) != (Cout, 3, 3, Cin) or not w_krsc.is_contiguous():
-        raise ValueError(f"conv3x3: w must be contiguous [Cout,3,3,{Cin}], got {tuple(w_krsc.shape)}")
+    phases = upsample2x is not True and int(upsample2x) == 2       # the phase form: w is repack.upsample_phase_pack's [4,Cout,2,2,Cin]
+    Cout = w_krsc.shape[1 if phases else 0]
+    if tuple(w_krsc.shape) != ((4, Cout, 2, 2, Cin) if phases else (Cout, 3, 3, Cin)) or not w_krsc.is_contiguous():
+        raise ValueError(f"conv3x3: w must be contiguous {'[4,Cout,2,2,' if phases else '[Cout,3,3,'}{Cin}], got {tuple(w_krsc.shape)}")
     hin, win = (H * 2, W * 2) if upsample2x else (H, W)
     Ho, Wo = (hin - 1) // stride + 1, (win - 1) // stride + 1
     if tuple(out.shape) != (B, Ho, Wo, Cout):
@@ -448,18 +453,21 @@ def _conv_desc(x: torch.Tensor, w_krsc: torch.Tensor, out: torch.Tensor, *, stri
         TUNE_SINK.append((sig, dict(kind="conv", B=B, H=H, W=W, Cin=Cin, Cout=Cout, stride=stride, ups=bool(upsample2x), padded=bool(x_padded),
                                     out_f32=bool(flags & F_OUT_F32), bias=bias is not None, rowbias=rowbias is not None,
                                     res1=None if res1 is None else str(res1.dtype))))
-    return d, 2.0 * B * Ho * Wo * Cout * 9 * Cin, f"B{B} {Ho}x{Wo} {Cin}->{Cout} s{stride}{' up' if upsample2x else ''}"
+    # (the phase form executes 4 of the 9 taps: its FLOPs are reported as executed)
+    return d, 2.0 * B * Ho * Wo * Cout * (4 if phases else 9) * Cin, f"B{B} {Ho}x{Wo} {Cin}->{Cout} s{stride}{(' up4' if phases else ' up') if upsample2x else ''}"
 
 
 def conv3x3(x: torch.Tensor, w_krsc: torch.Tensor, out: torch.Tensor, **kw) -> torch.Tensor:
     """x [B,H,W,Cin] (channels-last, pixel-strided view allowed; or the zero-bordered [B,H+2,W+2,Cin] with
-    x_padded=True) -> out [B,Ho,Wo,Cout] (fp16 or fp32); w_krsc [Cout,3,3,Cin]; res1 fp16 or fp32.  Keywords: stride, upsample2x,
+    x_padded=True) -> out [B,Ho,Wo,Cout] (fp16 or fp32); w_krsc [Cout,3,3,Cin]; res1 fp16 or fp32.  Keywords: stride, upsample2x
+    (True: nearest 2x folded into the gather; 2: the same result as four 2x2 phase convolutions, w_krsc = repack.upsample_phase_pack's
+    [4,Cout,2,2,Cin], x_padded and bias only — sg_conv3x3_desc.upsample2x; conv3x3_upsample picks between the two),
     bias, rowbias, res1, split_k, workspace, x_padded, tile, stats (fp32 buffer: GroupNorm partial statistics of the output),
     defer_reduce (a split-K launch leaves its partial tiles in the workspace for groupnorm(split=...): sg_conv3x3_desc.defer_reduce)."""
     d, flops, shape = _conv_desc(x, w_krsc, out, **kw)
     if PLAN_SINK is not None:
         Ho, Wo = out.shape[1], out.shape[2]
-        nb = 2.0 * d.B * d.H * d.W * d.Cin + 2.0 * d.Cout * 9 * d.Cin + (4 if d.flags & F_OUT_F32 else 2) * d.B * Ho * Wo * d.Cout
+        nb = 2.0 * d.B * d.H * d.W * d.Cin + 2.0 * d.Cout * (16 if d.upsample2x == 2 else 9) * d.Cin + (4 if d.flags & F_OUT_F32 else 2) * d.B * Ho * Wo * d.Cout
         if d.res1:
             nb += (4 if d.flags & F_RES1_F32 else 2) * d.B * Ho * Wo * d.Cout
         _report_plan("conv", d, nb, "conv3x3", shape)
@@ -470,6 +478,25 @@ def conv3x3(x: torch.Tensor, w_krsc: torch.Tensor, out: torch.Tensor, **kw) -> t
         else:
             check(lib.sg_conv3x3_nhwc_f16(C.byref(d), _stream()), "sg_conv3x3_nhwc_f16")
     return out
+
+
+def conv3x3_phases_fit(x: torch.Tensor, w_phases: torch.Tensor, out: torch.Tensor, **kw) -> bool:
+    """Does the phase form (upsample2x=2) have a launch for these arguments?  (sg_conv3x3_launch_plan; no launch.)  False when no row tile
+    of the LDS-DMA kernels divides the H W pixels of the input (SG_EUNSUP); an invalid descriptor raises as conv3x3 would."""
+    d, _, _ = _conv_desc(x, w_phases, out, **{**kw, "upsample2x": 2})
+    rc = lib.sg_conv3x3_launch_plan(C.byref(d), (C.c_int32 * 6)())
+    if rc == EUNSUP:
+        return False
+    check(rc, "sg_conv3x3_launch_plan")
+    return True
+
+
+def conv3x3_upsample(x: torch.Tensor, w_krsc: torch.Tensor, w_phases: torch.Tensor, out: torch.Tensor, **kw) -> torch.Tensor:
+    """Nearest-2x upsampling + 3x3 convolution of the zero-bordered x: the phase form on w_phases (repack.upsample_phase_pack) where it has a
+    launch, else conv3x3(..., upsample2x=True) on w_krsc.  Keywords as conv3x3 (no stride / upsample2x)."""
+    if conv3x3_phases_fit(x, w_phases, out, **kw):
+        return conv3x3(x, w_phases, out, upsample2x=2, **kw)
+    return conv3x3(x, w_krsc, out, upsample2x=True, **kw)
 
 
 def conv3x3_planned_splits(x: torch.Tensor, w_krsc: torch.Tensor, out: torch.Tensor, **kw) -> int:

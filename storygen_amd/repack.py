@@ -12,6 +12,37 @@ def conv3x3_krsc(w: torch.Tensor) -> torch.Tensor:
     return w.permute(0, 2, 3, 1).contiguous()
 
 
+# Taps of a 3x3 kernel row (or column) that land on source offset t in {0, 1} for output parity a in {0, 1} after nearest-2x
+# upsampling: output row 2i + a reads upsampled rows 2i + a - 1 + ky, i.e. source rows (2i + a - 1 + ky) >> 1 =
+#   a = 0: ky 0 -> i - 1 | ky 1, 2 -> i          a = 1: ky 0, 1 -> i | ky 2 -> i + 1
+# and offset t counts from the first of the two source rows (i - 1 + a).
+UPSAMPLE_PHASE_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))      # [a][t] -> tuple of ky
+
+
+def upsample_phase_sums(w: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> [4, Cout, 2, 2, Cin] in w's dtype, no rounding beyond that dtype's own: phase 2a + b, tap (ty, tx) holds the
+    sum of the taps (ky, kx) with ky in UPSAMPLE_PHASE_TAPS[a][ty], kx in UPSAMPLE_PHASE_TAPS[b][tx].  Nearest-2x upsampling followed
+    by the 3x3 convolution is, for output pixels (2i + a, 2j + b), the 2x2 convolution of the INPUT-resolution image with these weights
+    whose tap (ty, tx) reads source pixel (i - 1 + a + ty, j - 1 + b + tx) (zero outside the image)."""
+    cout, cin = w.shape[:2]
+    out = w.new_zeros(4, cout, 2, 2, cin)
+    for a in range(2):
+        for b in range(2):
+            for ty in range(2):
+                for tx in range(2):
+                    acc = out[2 * a + b, :, ty, tx]
+                    for ky in UPSAMPLE_PHASE_TAPS[a][ty]:
+                        for kx in UPSAMPLE_PHASE_TAPS[b][tx]:
+                            acc += w[:, :, ky, kx]
+    return out
+
+
+def upsample_phase_pack(w: torch.Tensor) -> torch.Tensor:
+    """The weights of an Upsample2D convolution for the phase form of sg_conv3x3_nhwc_f16 (upsample2x = 2): [4, Cout, 2, 2, Cin] fp16,
+    the tap sums formed in fp32 and rounded to fp16 once."""
+    return upsample_phase_sums(w.float()).to(torch.float16).contiguous()
+
+
 def conv_in_kn(w: torch.Tensor) -> torch.Tensor:
     """[Cout, Cin, 3, 3] -> [9*Cin, Cout] with k = (ky*3 + kx)*Cin + ci."""
     cout, cin = w.shape[:2]
